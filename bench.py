@@ -20,6 +20,14 @@ Launch (the driver does this):
 Rank 0 prints ONE JSON line with the whole-node call rate
 (value = evals/sec * n_gpus: each federated evaluation is one worker-call
 per GPU shard; weak scaling -- per-GPU rows fixed as N grows).
+
+A plain run does only what that figure needs: set up, warm up, time the
+``--steps`` evaluations, print the line.  ``--full`` adds the measurements
+that take runs of their own (multi-rank: the per-call all-reduce latency
+probe reported as ``config.allreduce_us``).  ``--dump-outputs DIR`` writes
+what the last timed step returned to its caller as ``DIR/logp.npy`` and
+``DIR/grad.npy`` (float64); inputs are seeded, so two builds run with the
+same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -47,7 +55,34 @@ def parse_args():
         help="skip per-step host readback (measures enqueue throughput only; "
         "NOT the headline metric)",
     )
-    return p.parse_known_args()[0]
+    p.add_argument(
+        "--full",
+        action="store_true",
+        help="also run the measurements beyond the headline figure "
+        "(multi-rank all-reduce latency probe)",
+    )
+    p.add_argument(
+        "--dump-outputs",
+        metavar="DIR",
+        default=None,
+        help="write the last timed step's [logp, grads] as DIR/logp.npy and DIR/grad.npy",
+    )
+    args = p.parse_known_args()[0]
+    if args.steps < 1:
+        p.error("--steps must be >= 1")
+    return args
+
+
+def result_arrays(res):
+    """(logp, grad) float64 arrays from what one evaluation handed its caller:
+    a (logp, d/da, d/db) tuple, a (logp, grad) pair, or a [logp, *grads] buffer."""
+    if isinstance(res, torch.Tensor):
+        flat = res.detach().to("cpu", torch.float64).numpy().reshape(-1)
+        return flat[:1].reshape(()).copy(), flat[1:].copy()
+    if len(res) == 2 and np.ndim(res[1]) > 0:
+        return np.asarray(res[0], dtype=np.float64), np.array(res[1], dtype=np.float64)
+    flat = np.array([float(v) for v in res], dtype=np.float64)
+    return flat[0].reshape(()), flat[1:]
 
 
 def main():
@@ -222,14 +257,14 @@ def main():
             if have_gpu:
                 torch.cuda.synchronize()
             return host_buf
-        return None
+        return buf
 
-    # Per-call collective cost (multi-rank only): mean wall time of one
+    # Per-call collective cost (multi-rank, --full only): mean wall time of one
     # eager all_reduce of the 3..K-double [logp, grads] buffer, measured
     # outside the bench loop so SCALE runs carry the latency diagnostic
     # whichever path (graphed or engine) the steps take.
     allreduce_us = None
-    if distributed:
+    if distributed and args.full:
         import torch.distributed as dist
 
         probe = torch.zeros(
@@ -264,10 +299,17 @@ def main():
         one_step(t)
     barrier_sync()
     t0 = time.perf_counter()
+    last = None
     for t in range(args.steps):
-        one_step(t)
+        last = one_step(t)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and rank == 0:
+        logp_arr, grad_arr = result_arrays(last)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "logp.npy"), logp_arr)
+        np.save(os.path.join(args.dump_outputs, "grad.npy"), grad_arr)
 
     # MAX over ranks
     if distributed:
