@@ -1367,6 +1367,8 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v2(
 // three 32-KB half-buffers with COUNTED vmcnt waits and raw s_barriers (a
 // __syncthreads with a glds in flight drains the whole queue -- guide
 // "Pipelining across barriers").  1 block/CU, contiguous tile ranges.
+// The counts (8 DMAs per wave per staged half) hold for full tiles only;
+// the problem's tail tile is processed outside the counted pipeline.
 //
 // Bank swizzle: the pad-free glds image (row stride 512 u16 == 0 mod 64
 // dwords) would put every row on the same banks, so the SOURCE column
@@ -1468,7 +1470,10 @@ __device__ __forceinline__ void v3_stage_half(
 
 // v4 staging: one 1-KB DMA = 4 rows x 128 cols landing as 8 contiguous
 // [4][16] subtiles; per wave 8 DMAs (row-groups 2w..2w+1 x 4 col-octets),
-// so the v3 vmcnt ledgers hold unchanged.  Lane n supplies the source of
+// so the v3 vmcnt ledgers hold unchanged on full tiles.  On the tail tile
+// a wave issues 4 DMAs per fully valid row-group and none for an edge one
+// (v3_stage_half: one per valid row), so the kernel keeps the tail tile
+// out of the counted pipeline.  Lane n supplies the source of
 // image element n*8: subtile s = n>>3, row j = (n&7)>>1, col-half h = n&1.
 __device__ __forceinline__ void v4_stage_half(
     const unsigned short* __restrict__ X, long long n_rows, int K,
@@ -1580,16 +1585,29 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3s(
         }
     };
 
-    if (t_begin < t_end) {
-        stage_tile(t_begin * V3_ROWS, 0);
-        if (t_begin + 1 < t_end) stage_tile((t_begin + 1) * V3_ROWS, 1);
+    // The counted waits below assume 8 DMAs per wave per staged tile; the
+    // problem's TAIL tile stages one DMA per VALID row (0..8 per wave), so
+    // a vmcnt(8) counted against it waits for too little.  As in v3 it is
+    // kept out of the counted pipeline: pass 0 runs this block's FULL tiles,
+    // pass 1 the tail tile alone (a one-tile range only ever waits with
+    // vmcnt(0)).  Both ranges are block-uniform.
+    const long long n_full = n_rows / V3_ROWS;  // tiles with every row valid
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long p_begin = pass == 0 ? t_begin : (t_begin > n_full ? t_begin : n_full);
+        const long long p_end = pass == 0 ? (t_end < n_full ? t_end : n_full) : t_end;
+        if (p_begin >= p_end) continue;
+        // pass 1 restages buffer 0: pass 0 ended drained and behind its
+        // closing barrier, so the buffer is free
+        stage_tile(p_begin * V3_ROWS, 0);
+        if (p_begin + 1 < p_end) stage_tile((p_begin + 1) * V3_ROWS, 1);
 
 #pragma unroll 1
-        for (long long tile = t_begin; tile < t_end; ++tile) {
+        for (long long tile = p_begin; tile < p_end; ++tile) {
             const long long row0 = tile * V3_ROWS;
-            unsigned short* xb = x_base + (int)((tile - t_begin) % 3) * TBUF;
-            const bool more1 = tile + 1 < t_end;
-            const bool more2 = tile + 2 < t_end;
+            unsigned short* xb = x_base + (int)((tile - p_begin) % 3) * TBUF;
+            const bool more1 = tile + 1 < p_end;
+            const bool more2 = tile + 2 < p_end;
 
             // [a] own tile's DMAs complete; newer: t+1's (8/RPD) if issued
             if (more1) V3_ASM_VMCNT(8); else V3_ASM_VMCNT(0);
@@ -1600,7 +1618,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3s(
             long long yr1 = row0 + 16 + (threadIdx.x >> 4);
             const unsigned yb0 = v3_load_y_asm(y + (yr0 > ymax ? ymax : yr0));
             const unsigned yb1 = v3_load_y_asm(y + (yr1 > ymax ? ymax : yr1));
-            if (more2) stage_tile((tile + 2) * V3_ROWS, (int)((tile + 2 - t_begin) % 3));
+            if (more2) stage_tile((tile + 2) * V3_ROWS, (int)((tile + 2 - p_begin) % 3));
 
             // ---- phase A: complete Z over this wave's K-quarter ----
             f32x4_t z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
@@ -1771,25 +1789,46 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
     const long long t_begin = blockIdx.x * tpb;
     const long long t_end = t_begin + tpb < n_tiles ? t_begin + tpb : n_tiles;
 
-    if (t_begin < t_end) {
-        // prologue: stage tile t_begin fully.  h0 buffers alternate 0/2,
+    // The counted vmcnt waits of the tile loop assume 8 DMAs per wave per
+    // staged half.  The problem's TAIL tile (fewer than V3_ROWS valid rows)
+    // breaks that: a wave issues one DMA per valid row (v3 image) or 4 per
+    // fully valid row-group (v4 image) and fills the rest with LDS stores,
+    // so it owns anywhere from 0 to 8 -- a vmcnt(8) counted against such a
+    // half waits for too little and phase A may read rows that have not
+    // landed.  The tail tile therefore never enters the counted pipeline:
+    // pass 0 runs this block's FULL tiles with the exact ledger, pass 1
+    // runs the tail tile (owned by one block) on its own, fully drained
+    // before its first gate.  Both ranges are block-uniform.
+    const long long n_full = n_rows / V3_ROWS;  // tiles with every row valid
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+        const long long p_begin = pass == 0 ? t_begin : (t_begin > n_full ? t_begin : n_full);
+        const long long p_end = pass == 0 ? (t_end < n_full ? t_end : n_full) : t_end;
+        if (p_begin >= p_end) continue;
+        // pass 1 restages buffers 0/1: every wave must be done with pass 0's
+        // phase-B reads (pass 0 ends fully drained: its last [4] is vmcnt(0))
+        if (pass) V3_BARRIER();
+        // prologue: stage tile p_begin fully.  h0 buffers alternate 0/2,
         // h1 lives in buffer 1.
         if constexpr (TRB) {
-            v4_stage_half(X, n_rows, K, t_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
-            v4_stage_half(X, n_rows, K, t_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane, nt_on);
+            v4_stage_half(X, n_rows, K, p_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
+            v4_stage_half(X, n_rows, K, p_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane, nt_on);
         } else {
-            v3_stage_half(X, n_rows, K, t_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
-            v3_stage_half(X, n_rows, K, t_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane, nt_on);
+            v3_stage_half(X, n_rows, K, p_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
+            v3_stage_half(X, n_rows, K, p_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane, nt_on);
         }
+        // the tail tile's short halves cannot be counted: drain them here,
+        // which makes its gate [1] trivially true
+        if (pass) V3_ASM_VMCNT(0);
 
         int h0sel = 0;  // buffer index (0 or 2) holding the CURRENT tile's h0
 #pragma unroll 1
-        for (long long tile = t_begin; tile < t_end; ++tile) {
+        for (long long tile = p_begin; tile < p_end; ++tile) {
             const long long row0 = tile * V3_ROWS;
             unsigned short* h0 = x_base + h0sel * HBUF;
             unsigned short* h1 = x_base + HBUF;
             unsigned short* h0n = x_base + (h0sel ^ 2) * HBUF;  // next tile's h0
-            const bool more = tile + 1 < t_end;
+            const bool more = tile + 1 < p_end;
 
             // [1] own h0 DMAs done (h1's 8 may stay in flight), all waves
             unsigned long long pt = 0;
@@ -1843,8 +1882,10 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                 p_phA += __builtin_amdgcn_s_memtime() - pa;
             // [4] own h1 DMAs + y loads done.  The count must match what
             // was actually issued after them: 8 prefetch DMAs on interior
-            // tiles, NOTHING on the last tile (an unconditional vmcnt(8)
-            // there would leave h1/y unwaited -- a timing-dependent race).
+            // tiles (the prefetched tile is always a full one -- the tail
+            // tile is kept out of this pass), NOTHING on the last tile (an
+            // unconditional vmcnt(8) there would leave h1/y unwaited -- a
+            // timing-dependent race).
             if (prof_on && wid == 0 && lane == 0) pt = __builtin_amdgcn_s_memtime();
             if (more) V3_ASM_VMCNT(8); else V3_ASM_VMCNT(0);
             V3_BARRIER();

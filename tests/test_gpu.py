@@ -81,6 +81,10 @@ class TestLogisticKernel:
         (torch.bfloat16, 512, 2e-4),
         (torch.bfloat16, 1024, 2e-4),
         (torch.float32, 1024, 1e-5),
+        # appended, so the ids of the cases above stay what they were
+        (torch.float32, 256, 1e-5),
+        (torch.float32, 512, 1e-5),
+        (torch.bfloat16, 2048, 2e-4),
     ])
     def test_matches_eager_same_data(self, dev, dtype, K, rtol):
         X, y, beta0 = generate_logistic_dataset(20_000, K, seed=23)
