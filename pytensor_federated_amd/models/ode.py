@@ -175,19 +175,29 @@ class ODEModel(LogpGradModel):
         y = torch.as_tensor(np.asarray(y_obs)) if not isinstance(y_obs, torch.Tensor) else y_obs
         if device is None:
             device = u0.device
-        self._u0 = u0.to(device=device, dtype=dtype)
-        self._y = y.to(device=device, dtype=dtype)
+        if u0.dim() != 2:
+            raise ValueError(f"u0 must be [B, D], got shape {tuple(u0.shape)}")
+        # contiguous: the native kernels read these through data_ptr() as
+        # C-ordered [B][D] / [n_obs][B][D]
+        self._u0 = u0.to(device=device, dtype=dtype).contiguous()
+        self._y = y.to(device=device, dtype=dtype).contiguous()
         self._t0 = float(t0)
         self._h = (float(t1) - float(t0)) / int(n_steps)
         self._n_steps = int(n_steps)
         self._obs_idx = [int(i) for i in obs_indices]
-        if sorted(self._obs_idx) != self._obs_idx:
-            raise ValueError("obs_indices must be sorted ascending.")
+        if any(b <= a for a, b in zip(self._obs_idx, self._obs_idx[1:])):
+            raise ValueError("obs_indices must be strictly ascending (no duplicates).")
+        if self._obs_idx and not (0 <= self._obs_idx[0] and self._obs_idx[-1] <= self._n_steps):
+            raise ValueError(f"obs_indices must lie within 0..{self._n_steps}.")
+        n_comp = u0.shape[1] if obs_components is None else len(obs_components)
+        want = (len(self._obs_idx), u0.shape[0], n_comp)
+        if tuple(self._y.shape) != want:
+            raise ValueError(f"y_obs must be [n_obs, B, n_comp] = {want}, got {tuple(y.shape)}")
         self._obs_components = obs_components
         self._sigma = float(sigma)
         self._dtype = dtype
         self._use_kernels = use_kernels
-        self._native_state = None  # lazy (obs_of_step, states_ws, out)
+        self._native_state = None  # lazy (obs_of_step, states_ws, unused)
 
     def _native_kind(self):
         """Which native CDNA4 forward+adjoint path applies: the hand-derived
@@ -210,6 +220,15 @@ class ODEModel(LogpGradModel):
             and self._u0.shape[-1] == self.f.D
         ):
             return "poly"
+        return None
+
+    def _n_theta(self) -> Optional[int]:
+        """Number of thetas the field takes, where it is known (the kernels
+        read exactly that many)."""
+        if isinstance(self.f, PolynomialRHS):
+            return self.f.P
+        if self.f is lotka_volterra_rhs:
+            return 4
         return None
 
     def _native_path(self) -> bool:
@@ -261,12 +280,14 @@ class ODEModel(LogpGradModel):
             self._native_state = (
                 obs_of_step.to(self._u0.device),
                 torch.empty((self._n_steps + 1) * B * 2, dtype=torch.float64, device=self._u0.device),
-                torch.empty(5, dtype=torch.float64, device=self._u0.device),
+                None,
             )
-        obs_of_step, states_ws, out = self._native_state
-        ode_lv_logp_grad(
+        obs_of_step, states_ws, _ = self._native_state
+        # out is allocated per call (as on the poly path): the returned
+        # gradient is a view of it and must not alias what a later call writes
+        out = ode_lv_logp_grad(
             self._u0, self._y, obs_of_step, self._n_steps, self._h, self._sigma,
-            theta, states_ws, out=out,
+            theta, states_ws,
         )
         n_vals = self._y.numel()
         logp_const = -0.5 * n_vals * _math.log(2.0 * _math.pi * self._sigma**2)
@@ -340,6 +361,9 @@ class ODEModel(LogpGradModel):
 
     def logp_grad(self, theta) -> Tuple[torch.Tensor, List[torch.Tensor]]:
         theta = torch.as_tensor(theta).to(device=self.device, dtype=self._dtype)
+        n_par = self._n_theta()
+        if n_par is not None and theta.numel() != n_par:
+            raise ValueError(f"theta must have {n_par} elements, got shape {tuple(theta.shape)}")
         if self._native_path():
             return self._logp_grad_native(theta)
         states = self._forward_states(theta)

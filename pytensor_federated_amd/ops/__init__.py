@@ -247,6 +247,13 @@ def publish_result(buf: torch.Tensor, mailbox: "_np.ndarray", epoch_dev: torch.T
     _check(rc, "fed_publish_result")
 
 
+def _require_contiguous(**tensors: torch.Tensor) -> None:
+    """The kernels read these through data_ptr() as C-ordered arrays."""
+    for name, t in tensors.items():
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous (strides {t.stride()})")
+
+
 def ode_lv_logp_grad(
     u0: torch.Tensor,          # [B, 2] f64
     y_obs: torch.Tensor,       # [n_obs, B, 2] f64
@@ -263,6 +270,7 @@ def ode_lv_logp_grad(
     (The logp normalization constant is added by the caller.)
     """
     lib = require_kernels()
+    _require_contiguous(u0=u0, y_obs=y_obs, obs_of_step=obs_of_step, states_ws=states_ws)
     B = u0.shape[0]
     theta_dev = theta.detach().to(device=u0.device, dtype=torch.float64).contiguous()
     if out is None:
@@ -302,6 +310,7 @@ def ode_poly_logp_grad(
     The logp normalization constant is added by the caller.
     """
     lib = require_kernels()
+    _require_contiguous(u0=u0, y_obs=y_obs, obs_of_step=obs_of_step, states_ws=states_ws)
     B = u0.shape[0]
     T = len(terms)
     d_arr = (ctypes.c_int * T)(*[int(t[0]) for t in terms])
@@ -416,6 +425,7 @@ def ode_lv_logp_grad_batched(
 ) -> torch.Tensor:
     """Batched native Lotka-Volterra: C thetas in one sweep -> [C][5]."""
     lib = require_kernels()
+    _require_contiguous(u0=u0, y_obs=y_obs, obs_of_step=obs_of_step, states_ws=states_ws)
     B = u0.shape[0]
     C = theta_c.shape[0]
     theta_dev = theta_c.detach().to(device=u0.device, dtype=torch.float64).contiguous()

@@ -194,10 +194,11 @@ __global__ __launch_bounds__(256) void k_lv_adjoint(
 }
 
 // Batched variant: C chains (thetas) x B experiments in one sweep.  Lane
-// l handles (chain = l / B, experiment = l % B); with B a multiple of 256
-// every block belongs to one chain, so the block reduction can target that
-// chain's output slot directly.  Fills the chip (B*C lanes) where the
-// single-theta kernel at B=1024 only occupies 4 CUs.
+// l handles (chain = l / B, experiment = l % B) for any B and C: there is no
+// block reduction here, every lane adds its own contribution to its chain's
+// output slot atomically, so a block may hold lanes of several chains.
+// Fills the chip (B*C lanes) where the single-theta kernel at B=1024 only
+// occupies 4 CUs.
 __global__ __launch_bounds__(256) void k_lv_forward_batched(
     const double* __restrict__ u0,       // [B][2]
     const double* __restrict__ y_obs,    // [n_obs][B][2]
