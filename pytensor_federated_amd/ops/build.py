@@ -24,11 +24,14 @@ def sources():
     return sorted(CSRC.glob("*.hip"))
 
 
-def needs_rebuild() -> bool:
-    if not LIB_PATH.exists():
+def needs_rebuild(csrc: Path = CSRC, lib: Path = LIB_PATH) -> bool:
+    """True when ``lib`` is missing or older than any ``.hip`` source or
+    shared ``.hpp`` header under ``csrc``."""
+    if not lib.exists():
         return True
-    lib_mtime = LIB_PATH.stat().st_mtime
-    return any(src.stat().st_mtime > lib_mtime for src in sources())
+    lib_mtime = lib.stat().st_mtime
+    inputs = list(csrc.glob("*.hip")) + list(csrc.glob("*.hpp"))
+    return any(src.stat().st_mtime > lib_mtime for src in inputs)
 
 
 WORKER_SRC = CSRC / "fed_worker.cpp"

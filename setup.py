@@ -31,7 +31,7 @@ setup(
     version="0.2.0",
     description="MI355X-native federated logp/gradient engine",
     packages=find_packages(include=["pytensor_federated_amd*"]),
-    package_data={"pytensor_federated_amd.ops": ["*.so", "csrc/*.hip"]},
+    package_data={"pytensor_federated_amd.ops": ["*.so", "csrc/*.hip", "csrc/*.hpp"]},
     python_requires=">=3.10",
     install_requires=["numpy", "psutil", "grpcio", "nest_asyncio"],
     cmdclass={"build_ext": BuildHip, "build_hip": BuildHip},
