@@ -345,8 +345,13 @@ class PersistentLinearEngine:
     request mailbox and spin-reads the pinned result mailbox -- no kernel
     launch, no stream sync, no ramp (the ~18 us fixed cost of the
     launch-per-eval path).  Every device spin is bounded: the server
-    self-exits after ~30-60 s idle and is relaunched transparently on the
+    self-exits after ~1-2 s idle and is relaunched transparently on the
     next call.
+
+    The shard is snapshotted at every (re)launch: each lane keeps its first
+    rows of ``x`` and ``y`` in registers and re-reads only what does not fit.
+    ``x`` and ``y`` must therefore not be mutated in place while the engine
+    is open -- close it and open a new one to serve changed data.
     """
 
     def __init__(self, x: torch.Tensor, y: torch.Tensor, sigma: float) -> None:
@@ -376,6 +381,9 @@ class PersistentLinearEngine:
         self._start()
 
     def _start(self) -> None:
+        # the server runs on a stream of its own and snapshots the shard as
+        # it launches: whatever produced x and y must have finished
+        torch.cuda.current_stream(self._x.device).synchronize()
         self._handle = self._lib.fed_gaussian_persistent_start(
             self._x.data_ptr(), self._y.data_ptr(), self._x.numel(),
             self._sigma, self._dtype_code,

@@ -75,6 +75,14 @@ template <> struct VecTraits<double> {
         out[0] = v.x; out[1] = v.y;
     }
     __device__ static inline double get(const double* p, long long i) { return p[i]; }
+    __device__ static inline void unpack(const u32x4_t v, double* out) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            union { unsigned long long u; double d; } c;
+            c.u = ((unsigned long long)v[2 * j + 1] << 32) | v[2 * j];
+            out[j] = c.d;
+        }
+    }
 };
 struct bf16_tag { unsigned short bits; };
 template <> struct VecTraits<bf16_tag> {
