@@ -342,11 +342,11 @@ class PersistentLinearEngine:
     """Resident eval-server kernel for one gaussian linear shard.
 
     The kernel stays launched; each call writes {seq, a, b} into a pinned
-    request mailbox and spin-reads the pinned result mailbox -- no kernel
+    request mailbox and spin-reads the pinned result line -- no kernel
     launch, no stream sync, no ramp (the ~18 us fixed cost of the
     launch-per-eval path).  Every device spin is bounded: the server
-    self-exits after ~1-2 s idle and is relaunched transparently on the
-    next call.
+    self-exits after 1.5 s idle and is relaunched transparently, at the
+    host's sequence, on the next call (``relaunch_count`` counts these).
 
     The shard is snapshotted at every (re)launch: each lane keeps its first
     rows of ``x`` and ``y`` in registers and re-reads only what does not fit.
@@ -369,6 +369,8 @@ class PersistentLinearEngine:
             ]
             lib.fed_gaussian_persistent_stop.restype = ctypes.c_int
             lib.fed_gaussian_persistent_stop.argtypes = [ctypes.c_void_p]
+            lib.fed_gaussian_persistent_relaunch_count.restype = ctypes.c_int
+            lib.fed_gaussian_persistent_relaunch_count.argtypes = [ctypes.c_void_p]
             lib.fed_gaussian_persistent_start._cfg = True
         self._lib = lib
         assert x.is_cuda and x.is_contiguous() and y.is_contiguous()
@@ -407,6 +409,14 @@ class PersistentLinearEngine:
             if rc != 0:
                 raise RuntimeError(f"persistent eval failed ({rc})")
             return self._out[0], self._out[1], self._out[2]
+
+    @property
+    def relaunch_count(self) -> int:
+        """Times the server was launched again after an idle self-exit."""
+        with self._lock:
+            if not self._handle:
+                return 0
+            return int(self._lib.fed_gaussian_persistent_relaunch_count(self._handle))
 
     def close(self) -> None:
         if getattr(self, "_handle", None):

@@ -567,11 +567,57 @@ int fed_ipc_close(void* dev_ptr) { return (int)hipIpcCloseMemHandle(dev_ptr); }
 // (launch + wave ramp + drain) against ~7 us of actual streaming at 1e7
 // rows -- the boundary dominates, which is the canonical persistent-kernel
 // case.  This kernel stays resident (512 blocks = 2/CU, all the resident
-// shard's registers admit): block 0 polls a pinned host
-// request mailbox, broadcasts {seq, theta} through device memory (sc1
-// granules), every block computes its grid-stride partials, the
-// last-arriver combines and publishes to the pinned result mailbox, and a
-// device done-flag releases the blocks into the next iteration.
+// shard's registers admit) and serves one request per loop iteration.
+//
+// PROTOCOL.  Every hand-off is a set of 8-byte GRANULES {tag << 32 | 32-bit
+// value}, tag = low 32 bits of the call's sequence number, each written by
+// ONE aligned 8-byte agent-scope store from a lane and read by a relaxed
+// agent-scope load: the data is the flag.  There is no separate flag word, no
+// store drain, no fence, no atomic read-modify-write.  A 64-bit value is two
+// granules; a reader accepts a value only when the tags of ALL its own
+// granules equal the call's tag, never on a neighbour's.
+//   1. request    host -> block 0: pinned [seq | a | b | seq_pre] seqlock,
+//                 polled by block 0's first wave (FED_PK_SEQLOCK=0: lane 0
+//                 detects seq, then reads a, b).
+//   2. broadcast  block 0 -> all: ONE 64-byte line of five granules {a lo,
+//                 a hi, b lo, b hi, control (0 serve, 1 quit)}, stored by
+//                 lanes 0..4 of one wave with one store instruction; every
+//                 other block's first wave polls it with one wave-wide load.
+//   3. compute    from the register-resident shard (below).
+//   4. partials   every block (block 0 too) -> its own 64-byte slot: three
+//                 f64 block sums as six granules, one store instruction.
+//   5. combine    block 0 is the FIXED combiner: thread t owns the slots of
+//                 blocks t, t+256, ..., re-reads those whose six tags are not
+//                 yet all current, and adds them in increasing block index
+//                 from 0.0; then the block reduction -- the summation order
+//                 of the former last-arriver combine, so results are
+//                 bit-identical to it.
+//   6. publish    block 0 -> host: [logp, ga, gb] as six granules plus a
+//                 seventh {tag, code} word in one 64-byte pinned line, one
+//                 store instruction; the host spins until all six tags are
+//                 its sequence's.  code != 0 under the awaited tag means the
+//                 server gave up (1 idle exit or quit, 2 combine timeout).
+//
+// WHY NO COMPLETION BARRIER.  Slot and line reuse is ordered by causality:
+//   - a worker stores call s+1's granules only after it has seen broadcast
+//     s+1;
+//   - block 0 issues broadcast s+1 only after the host has sent request s+1;
+//   - the host sends request s+1 only after it has received result s;
+//   - block 0 publishes result s only after its sweep of call s is complete,
+//     i.e. after it has read every slot of call s, each of which was stored
+//     by a block that had read broadcast s.
+// So nobody overwrites a granule that a reader of the previous call still
+// needs, and a reader can only ever see "previous call" or "this call".
+//
+// INIT INVARIANT.  In the steady state every tag in the three tagged areas
+// (broadcast line, partial slots, result line) names the previous call.
+// The host establishes exactly that before every (re)launch: a small kernel
+// on the server's stream sets every tag to the low 32 bits of the last
+// served sequence, and the server starts counting from that sequence
+// (kernel argument).  Tags are compared for equality only, so the 32-bit
+// wrap is harmless, and a relaunched server can never take a granule left
+// by the exited one for current.  Zeroing would not do: 0 is a valid tag
+// once per 2^32 calls.
 //
 // RESIDENT SHARD.  The server serves one immutable shard, so each lane
 // loads its first PK_CAP 16-byte vectors of x and of y ONCE, before the
@@ -584,29 +630,38 @@ int fed_ipc_close(void* dev_ptr) { return (int)hipIpcCloseMemHandle(dev_ptr); }
 // CONTRACT: the shard is snapshotted at (re)launch -- x and y must not be
 // mutated in place while the server is open.
 //
-// The 512 blocks must all be co-resident (every block spins on flags other
+// The 512 blocks must all be co-resident (every block spins on words other
 // blocks publish): __launch_bounds__(256, 2) caps the registers so 2
 // blocks fit a CU, and fed_gaussian_persistent_start checks the occupancy
 // query against the grid before launching.
 //
-// EVERY spin is bounded: on exceeding its budget a block gives up and
-// exits (block 0 stamps a timeout code into the result mailbox), so the
-// kernel can never hang the GPU.  The host evaluator likewise times out
-// and shuts the server down.
+// EVERY spin is bounded, in ticks of the constant-rate clock (100 MHz)
+// sampled every PK_CLOCK_EVERY polls, and the bounds are ORDERED so that
+// block 0 always decides: its request poll (the idle lifetime) and its
+// combine sweep are far shorter than the workers' broadcast poll, and on
+// either give-up block 0 broadcasts the quit control word, which releases
+// every worker at once.  A worker's own bound only matters if block 0 is
+// gone without a word.  The host evaluator likewise times out and shuts
+// the server down.
 
 #define PK_SENTINEL 0xFFFFFFFFFFFFFFFFull
-// Spin bounds. The REQUEST poll doubles as the idle lifetime: a resident
-// kernel blocks any device-wide synchronize, so it exits after ~1-2 s idle
-// and the host relaunches it transparently (hipStreamQuery detects exit).
-#define PK_REQ_SPIN_LIMIT 2000000ll   // ~1-2 s idle at s_sleep(8) -> self-exit
-#define PK_SPIN_LIMIT 800000ll        // worker bcast poll (~1-2 s)
-#define PK_DONE_SPIN_LIMIT 200000ll   // completion barrier (compute is us-scale)
+// A resident kernel blocks any device-wide synchronize, so the request poll
+// doubles as the idle lifetime: block 0 exits after PK_IDLE_TICKS without a
+// request and the host relaunches the server transparently.
+#define PK_TICKS_PER_MS 100000ll                  // wall_clock64(): 100 MHz
+#define PK_IDLE_TICKS (1500 * PK_TICKS_PER_MS)    // block 0 request poll: 1.5 s
+#define PK_SWEEP_TICKS (250 * PK_TICKS_PER_MS)    // combine sweep: 0.25 s (compute is us-scale)
+#define PK_BCAST_TICKS (6000 * PK_TICKS_PER_MS)   // workers: 6 s > 3x (idle + sweep)
+#define PK_CLOCK_EVERY 256                        // polls between clock samples
+// s_sleep quantum of the workers' broadcast poll (A/B in profiles/PROFILES.md)
+#ifndef PK_BCAST_SLEEP
+#define PK_BCAST_SLEEP 16
+#endif
 
-struct PersistentState {       // device memory
-    unsigned long long bcast_seq;   // sc1-published request broadcast
-    unsigned long long done_seq;    // sc1-published completion flag
-    double theta[2];
-};
+// control block (device memory, 64-bit words): [0..8) the broadcast line,
+// then one 8-word (64-byte) partial slot per block
+#define PK_CTL_SLOT0 8
+#define PK_CTL_WORDS(grid) (8 + 8 * (long long)(grid))
 
 __device__ __forceinline__ unsigned long long load_sc1_u64(const unsigned long long* p) {
     return __hip_atomic_load((const gu64_t*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -616,6 +671,51 @@ __device__ __forceinline__ void store_sc1_u64(unsigned long long* p, unsigned lo
     __hip_atomic_store((gu64_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// the pinned result line is read by the host: same form, system scope
+__device__ __forceinline__ void store_sys_u64(unsigned long long* p, unsigned long long v) {
+    __hip_atomic_store((gu64_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+__device__ __forceinline__ unsigned long long pk_granule(unsigned tag, unsigned value) {
+    return ((unsigned long long)tag << 32) | value;
+}
+
+__device__ __forceinline__ unsigned long long pk_f64_bits(double d) {
+    union { double d; unsigned long long u; } c;
+    c.d = d;
+    return c.u;
+}
+
+__device__ __forceinline__ double pk_f64_from_halves(unsigned long long lo, unsigned long long hi) {
+    union { unsigned long long u; double d; } c;
+    c.u = (hi << 32) | (lo & 0xFFFFFFFFull);
+    return c.d;
+}
+
+// 32-bit half `lane` (0..5) of three 64-bit words laid out lo, hi, lo, hi, ..
+__device__ __forceinline__ unsigned pk_half_of3(
+    unsigned long long w0, unsigned long long w1, unsigned long long w2, int lane
+) {
+    const unsigned long long w = lane < 2 ? w0 : (lane < 4 ? w1 : w2);
+    return (unsigned)((lane & 1) ? (w >> 32) : w);
+}
+
+// Stage timing (profiling build only, -DFED_PK_PROF): lane 0 of every block
+// stamps the constant-rate clock into its 8-word slot of a device buffer;
+// the slot always describes the last served call.  Slots: 0 request
+// accepted / broadcast seen, 1 compute done, 2 partial stored, 3 combine
+// done, 4 publish issued (3 and 4: the combining block only).
+#ifdef FED_PK_PROF
+#define PK_PROF_PARAM , unsigned long long* prof
+#define PK_PROF_ARG(e) , (e)->prof
+#define PK_PROF(slot) \
+    store_sc1_u64(&prof[8 * (long long)blockIdx.x + (slot)], wall_clock64());
+#else
+#define PK_PROF_PARAM
+#define PK_PROF_ARG(e)
+#define PK_PROF(slot)
+#endif
+
 // Resident 16-byte vector pairs per lane (one value for every dtype).  From
 // the compiler's output for gfx950 (bf16 / f32 / f64 instantiation, VGPRs):
 // 10 slots 166 / 160 / 148, 16 slots 230 / 208 / 196, 20 slots 256 / 240 /
@@ -623,6 +723,23 @@ __device__ __forceinline__ void store_sc1_u64(unsigned long long* p, unsigned lo
 // 16 is the largest with margin; it holds 1.68e7 bf16 rows at grid 512 --
 // the 1e7 flagship with headroom.
 #define PK_CAP 16
+
+// A spin's budget in constant-rate ticks, kept off the fast path: the clock
+// is read only every PK_CLOCK_EVERY polls and the first reading starts the
+// budget, so a poll that succeeds early never reads it.
+struct PkSpinBound {
+    long long t0 = 0;
+    unsigned polls = 0;
+    __device__ __forceinline__ bool expired(long long budget) {
+        if ((++polls % PK_CLOCK_EVERY) != 0) return false;
+        const long long now = wall_clock64();
+        if (t0 == 0) {
+            t0 = now;
+            return false;
+        }
+        return now - t0 > budget;
+    }
+};
 
 __device__ __forceinline__ unsigned long long pk_readlane_u64(unsigned long long v, int lane) {
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane);
@@ -639,12 +756,12 @@ __device__ __forceinline__ unsigned long long pk_readlane_u64(unsigned long long
 // seq_pre == seq has a consistent payload in hand (the mailbox is page-
 // aligned, so the four words share one 64-byte line).  Quit rides seq as
 // PK_SENTINEL.  Returns the accepted `next`, or PK_SENTINEL on quit or on
-// exceeding the spin bound.
+// exceeding the idle lifetime.
 __device__ __forceinline__ unsigned long long pk_poll_seqlock_wave(
     const volatile double* req_host, unsigned long long next, double& a_req, double& b_req
 ) {
     const volatile unsigned long long* words = (const volatile unsigned long long*)req_host;
-    long long spins = 0;
+    PkSpinBound bound;
     while (true) {
         unsigned long long w = 0;
         if (threadIdx.x < 4) w = words[threadIdx.x];
@@ -662,8 +779,18 @@ __device__ __forceinline__ unsigned long long pk_poll_seqlock_wave(
         if (rs < next)  // no new request yet: back off
             __builtin_amdgcn_s_sleep(8);
         // torn read (host mid-write): immediate re-poll
-        if (++spins > PK_REQ_SPIN_LIMIT) return PK_SENTINEL;
+        if (bound.expired(PK_IDLE_TICKS)) return PK_SENTINEL;
     }
+}
+
+// Sets every tag of the three tagged areas to `tag` (the last served
+// sequence), values 0: the steady-state invariant, before every (re)launch.
+__global__ __launch_bounds__(256) void k_persistent_init(
+    unsigned long long* ctl, long long ctl_words, unsigned long long* res_host, unsigned tag
+) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < ctl_words) store_sc1_u64(&ctl[i], pk_granule(tag, 0u));
+    if (i < 8) store_sys_u64(&res_host[i], pk_granule(tag, 0u));
 }
 
 template <typename T>
@@ -673,13 +800,12 @@ __global__ __launch_bounds__(256, 2) void k_gaussian_persistent(
     long long n,
     double inv_sig2,
     double logp_const,
-    double* __restrict__ slab,          // [grid][3] (ws)
-    unsigned* __restrict__ ticket,      // sharded tickets (ws)
-    PersistentState* __restrict__ st,   // device control block
+    unsigned long long* ctl,            // device: broadcast line + partial slots
     const volatile double* __restrict__ req_host,  // pinned seqlock: [seq | a | b | seq_pre] (seq==SENTINEL -> quit)
-    double* __restrict__ res_host,      // pinned: [logp ga gb | seq]
+    unsigned long long* res_host,       // pinned result line: 6 granules + {tag, code}
     int seqlock_on,                     // 1: one-round-trip poll; 0: detect-then-read
-    int fence_mode                      // 1: __threadfence_system publish; 0: store-drain
+    unsigned long long seq0             // the last sequence already served
+    PK_PROF_PARAM
 ) {
     using TR = VecTraits<T>;
     using A = typename TR::acc_t;
@@ -687,7 +813,7 @@ __global__ __launch_bounds__(256, 2) void k_gaussian_persistent(
     const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const long long gstride = (long long)gridDim.x * blockDim.x;
     const long long nvec = n / VEC;
-    __shared__ double lds[4 * 3 + 4];  // reduce scratch + {seq, a, b} bcast
+    __shared__ double lds[4 * 3 + 4];  // reduce scratch + {go, a, b} bcast
 
     // ---- snapshot this lane's resident slice (once per launch) ----------
     // Slot k holds vector gid + k*gstride of x and of y, packed as loaded.
@@ -709,74 +835,88 @@ __global__ __launch_bounds__(256, 2) void k_gaussian_persistent(
         }
     }
 
-#define PK_STAMP(code)     if (blockIdx.x == 0 && threadIdx.x == 0) ((volatile unsigned long long*)res_host)[4] = (code);
-    unsigned long long my_seq = 0;
-    PK_STAMP(1)
+    unsigned long long my_seq = seq0;
+    unsigned long long* const slot = ctl + PK_CTL_SLOT0 + 8 * (long long)blockIdx.x;
     while (true) {
-        // ---- acquire next request --------------------------------------
-        unsigned long long next = my_seq + 1;
-        if (blockIdx.x == 0) {
-            if (threadIdx.x < WAVE) {
-                // poll the HOST mailbox: the first wave together (seqlock,
-                // one read per poll that carries the payload) or its lane 0
+        // ---- acquire next request (first wave of every block) ----------
+        const unsigned tag = (unsigned)(my_seq + 1);
+        if (threadIdx.x < WAVE) {
+            // (opaque per request, like nres below: hoisted out of the
+            // request loop, the lane predicates of the granule stores and
+            // loads live in SGPR pairs and spill)
+            int lane = threadIdx.x;
+            asm volatile("" : "+v"(lane));
+            unsigned long long wa = 0, wb = 0;  // theta, as bits
+            unsigned ctrl = 0;                  // 0 serve, else leave
+            if (blockIdx.x == 0) {
+                // poll the HOST mailbox: the wave together (seqlock, one
+                // read per poll that carries the payload) or its lane 0
                 // alone (detect seq, then read the payload; quit rides seq
                 // as PK_SENTINEL so a poll is ONE host-memory read)
+                unsigned long long next = my_seq + 1;
                 double a_req = 0.0, b_req = 0.0;
                 if (seqlock_on) {
                     next = pk_poll_seqlock_wave(req_host, next, a_req, b_req);
-                } else if (threadIdx.x == 0) {
-                    long long spins = 0;
-                    while (true) {
-                        const unsigned long long rs =
-                            ((const volatile unsigned long long*)req_host)[0];
-                        if (rs == PK_SENTINEL) { next = PK_SENTINEL; break; }
-                        if (rs >= next) break;
-                        __builtin_amdgcn_s_sleep(8);
-                        if (++spins > PK_REQ_SPIN_LIMIT) { next = PK_SENTINEL; break; }
+                } else {
+                    if (lane == 0) {
+                        PkSpinBound bound;
+                        while (true) {
+                            const unsigned long long rs =
+                                ((const volatile unsigned long long*)req_host)[0];
+                            if (rs == PK_SENTINEL) { next = PK_SENTINEL; break; }
+                            if (rs >= next) break;
+                            __builtin_amdgcn_s_sleep(8);
+                            if (bound.expired(PK_IDLE_TICKS)) {
+                                next = PK_SENTINEL;
+                                break;
+                            }
+                        }
+                        if (next != PK_SENTINEL) {
+                            a_req = req_host[1];
+                            b_req = req_host[2];
+                        }
                     }
-                    if (next != PK_SENTINEL) {
-                        a_req = req_host[1];
-                        b_req = req_host[2];
-                    }
+                    next = pk_readlane_u64(next, 0);  // lane 0's answer, wave-wide
                 }
-                if (threadIdx.x == 0) {
-                    if (next != PK_SENTINEL) {
-                        // sc1 payload + drained sc1 flag (G16 R1: a plain
-                        // store + vmcnt drain is NOT cross-XCD visible)
-                        store_sc1_f64(&st->theta[0], a_req);
-                        store_sc1_f64(&st->theta[1], b_req);
-                        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                        store_sc1_u64(&st->bcast_seq, next);
-                        lds[12] = (double)1.0;
-                        lds[13] = a_req;
-                        lds[14] = b_req;
-                    } else {
-                        store_sc1_u64(&st->bcast_seq, PK_SENTINEL);
-                        lds[12] = -1.0;
-                    }
-                }
-            }
-        } else if (threadIdx.x == 0) {
-            // poll the DEVICE broadcast (one lane per block)
-            long long spins = 0;
-            unsigned long long bs;
-            while (true) {
-                bs = load_sc1_u64(&st->bcast_seq);
-                if (bs >= next || bs == PK_SENTINEL) break;
-                __builtin_amdgcn_s_sleep(16);
-                if (++spins > PK_SPIN_LIMIT) { bs = PK_SENTINEL; break; }
-            }
-            if (bs == PK_SENTINEL) {
-                lds[12] = -1.0;
+                ctrl = (next == PK_SENTINEL) ? 1u : 0u;
+                wa = pk_readlane_u64(pk_f64_bits(a_req), 0);
+                wb = pk_readlane_u64(pk_f64_bits(b_req), 0);
+                if (lane == 0 && ctrl == 0u) { PK_PROF(0) }
+                // the broadcast: five granules, one store instruction
+                const unsigned v = lane < 4 ? pk_half_of3(wa, wb, 0ull, lane) : ctrl;
+                if (lane < 5) store_sc1_u64(&ctl[lane], pk_granule(tag, v));
+                // idle exit or quit: tell the host under the tag it would wait for
+                if (ctrl != 0u && lane == 0) store_sys_u64(&res_host[6], pk_granule(tag, 1u));
             } else {
-                lds[12] = 1.0;
-                lds[13] = load_sc1_f64(&st->theta[0]);
-                lds[14] = load_sc1_f64(&st->theta[1]);
+                // poll the DEVICE broadcast line: one wave-wide load, accept
+                // when all five tags are this call's
+                PkSpinBound bound;
+                unsigned long long g = 0;
+                bool seen = false;
+                while (true) {
+                    if (lane < 5) g = load_sc1_u64(&ctl[lane]);
+                    const bool ok = lane >= 5 || (unsigned)(g >> 32) == tag;
+                    if (__all(ok)) { seen = true; break; }
+                    __builtin_amdgcn_s_sleep(PK_BCAST_SLEEP);
+                    if (bound.expired(PK_BCAST_TICKS)) break;
+                }
+                const unsigned lo = (unsigned)g;
+                wa = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)lo, 1) << 32) |
+                     (unsigned)__builtin_amdgcn_readlane((int)lo, 0);
+                wb = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)lo, 3) << 32) |
+                     (unsigned)__builtin_amdgcn_readlane((int)lo, 2);
+                ctrl = seen ? (unsigned)__builtin_amdgcn_readlane((int)lo, 4) : 2u;
+                if (lane == 0 && ctrl == 0u) { PK_PROF(0) }
+            }
+            if (lane == 0) {
+                lds[12] = ctrl == 0u ? 1.0 : -1.0;
+                lds[15] = 0.0;  // block 0's sweep-timeout word
+                lds[13] = pk_f64_from_halves(wa, wa >> 32);
+                lds[14] = pk_f64_from_halves(wb, wb >> 32);
             }
         }
         __syncthreads();
-        if (lds[12] < 0.0) return;  // quit or spin give-up
-        PK_STAMP(2)
+        if (lds[12] < 0.0) return;  // quit, idle exit or spin give-up
         const double a = lds[13];
         const double b = lds[14];
         __syncthreads();  // lds reused by the reduction below
@@ -808,85 +948,118 @@ __global__ __launch_bounds__(256, 2) void k_gaussian_persistent(
         sums.tail(x, y, n, gid, gstride, a, b);
         double sr, srx, sr2;
         sums.finish(sr, srx, sr2);
-        PK_STAMP(3)
+        if (threadIdx.x == 0) { PK_PROF(1) }
         double acc[3] = {sr2, sr, srx};
         block_reduce_add<3>(acc, lds);
-        bool last = false;
-        if (threadIdx.x == 0) {
-            double* s = slab + 3 * (long long)blockIdx.x;
-            store_sc1_f64(&s[0], acc[0]);
-            store_sc1_f64(&s[1], acc[1]);
-            store_sc1_f64(&s[2], acc[2]);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const unsigned ngroups = gridDim.x < 8 ? gridDim.x : 8;
-            const unsigned gsize = gridDim.x / ngroups;
-            const unsigned grp = blockIdx.x % ngroups;
-            const unsigned old = __hip_atomic_fetch_add(
-                (gu32_t*)(ticket + 16 * grp), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (old % gsize == gsize - 1) {
-                const unsigned t = __hip_atomic_fetch_add(
-                    (gu32_t*)(ticket + 16 * 8), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                last = (t % ngroups) == (ngroups - 1);
-            }
-            lds[12] = last ? 1.0 : 0.0;
+        // ---- partials: six granules into this block's slot ---------------
+        if (threadIdx.x < WAVE) {
+            int lane = threadIdx.x;
+            asm volatile("" : "+v"(lane));
+            const unsigned long long w0 = pk_readlane_u64(pk_f64_bits(acc[0]), 0);
+            const unsigned long long w1 = pk_readlane_u64(pk_f64_bits(acc[1]), 0);
+            const unsigned long long w2 = pk_readlane_u64(pk_f64_bits(acc[2]), 0);
+            if (lane < 6) store_sc1_u64(&slot[lane], pk_granule(tag, pk_half_of3(w0, w1, w2, lane)));
+            if (lane == 0) { PK_PROF(2) }
         }
-        __syncthreads();
+        if (blockIdx.x != 0) continue;
 
-        if (lds[12] != 0.0) {
-            // last-arriving block: combine + publish + release the others
-            double fin[3] = {0.0, 0.0, 0.0};
-            for (unsigned i = threadIdx.x; i < gridDim.x; i += blockDim.x) {
+        // ---- block 0: sweep the slots, combine, publish ------------------
+        // Thread t owns blocks t, t+256, ...; two slots are in flight per
+        // pass and only slots whose tags are not all current are re-read.
+        double fin[3] = {0.0, 0.0, 0.0};
+        bool timed_out = false;
+        {
+            PkSpinBound bound;
+            for (unsigned base = threadIdx.x; base < gridDim.x; base += 2 * 256) {
+                const unsigned long long* s0 = ctl + PK_CTL_SLOT0 + 8 * (long long)base;
+                const unsigned long long* s1 = s0 + 8 * 256;
+                const bool have1 = base + 256 < gridDim.x;
+                bool p0 = true, p1 = have1;
+                unsigned long long g0[6] = {0, 0, 0, 0, 0, 0}, g1[6] = {0, 0, 0, 0, 0, 0};
+                while (p0 || p1) {
+                    if (p0) {
 #pragma unroll
-                for (int k = 0; k < 3; ++k)
-                    fin[k] += load_sc1_f64(&slab[3 * (long long)i + k]);
-            }
-            __syncthreads();
-            block_reduce_add<3>(fin, lds);
-            if (threadIdx.x == 0) {
-                // volatile: inside the persistent loop the compiler defers /
-                // elides plain mailbox stores (measured: data landed, the
-                // plain u64 flag never did)
-                volatile double* rh = (volatile double*)res_host;
-                rh[0] = logp_const - 0.5 * inv_sig2 * fin[0];
-                rh[1] = inv_sig2 * fin[1];
-                rh[2] = inv_sig2 * fin[2];
-                if (fence_mode) {
-                    __threadfence_system();
-                } else {
-                    // store-drain instead of the system fence: same-box A/B
-                    // measured 55.4-55.8k vs 54.7-55.7k calls/s -- ~1%,
-                    // within rep noise, so the formally correct
-                    // __threadfence_system stays the default and this
-                    // path is kept only as the documented experiment
-                    // (FED_PK_FENCE=0)
-                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                        for (int k = 0; k < 6; ++k) g0[k] = load_sc1_u64(&s0[k]);
+                    }
+                    if (p1) {
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) g1[k] = load_sc1_u64(&s1[k]);
+                    }
+                    if (p0) {
+                        bool m = true;
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) m &= (unsigned)(g0[k] >> 32) == tag;
+                        p0 = !m;
+                    }
+                    if (p1) {
+                        bool m = true;
+#pragma unroll
+                        for (int k = 0; k < 6; ++k) m &= (unsigned)(g1[k] >> 32) == tag;
+                        p1 = !m;
+                    }
+                    if (p0 || p1) {
+                        __builtin_amdgcn_s_sleep(1);
+                        if (bound.expired(PK_SWEEP_TICKS)) {
+                            timed_out = true;
+                            break;
+                        }
+                    }
                 }
-                ((volatile unsigned long long*)res_host)[3] = my_seq;
-                store_sc1_u64(&st->done_seq, my_seq);
+                if (timed_out) break;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) fin[k] += pk_f64_from_halves(g0[2 * k], g0[2 * k + 1]);
+                if (have1) {
+#pragma unroll
+                    for (int k = 0; k < 3; ++k)
+                        fin[k] += pk_f64_from_halves(g1[2 * k], g1[2 * k + 1]);
+                }
             }
         }
-        PK_STAMP(4)
-        // ---- completion barrier (slab must not be reused early) ---------
-        if (threadIdx.x == 0) {
-            long long spins = 0;
-            while (load_sc1_u64(&st->done_seq) < my_seq) {
-                __builtin_amdgcn_s_sleep(8);
-                if (++spins > PK_DONE_SPIN_LIMIT) { lds[12] = -1.0; break; }
-            }
+        if (timed_out) lds[15] = 1.0;
+        __syncthreads();  // (also separates the two reductions' uses of lds)
+        if (lds[15] != 0.0) {
+            // give up: release the workers under the NEXT call's tag (the
+            // one they wait for), tell the host under this call's, exit
+            unsigned t = threadIdx.x;
+            asm volatile("" : "+v"(t));  // keep this cold path's predicates out of the loop's SGPRs
+            if (t < 5) store_sc1_u64(&ctl[t], pk_granule(tag + 1u, t == 4 ? 1u : 0u));
+            if (t == 0) store_sys_u64(&res_host[6], pk_granule(tag, 2u));
+            return;
         }
-        __syncthreads();
-        if (lds[12] < 0.0) return;
+        block_reduce_add<3>(fin, lds);
+        if (threadIdx.x < WAVE) {
+            int lane = threadIdx.x;
+            asm volatile("" : "+v"(lane));
+            const unsigned long long w0 =
+                pk_readlane_u64(pk_f64_bits(logp_const - 0.5 * inv_sig2 * fin[0]), 0);
+            const unsigned long long w1 = pk_readlane_u64(pk_f64_bits(inv_sig2 * fin[1]), 0);
+            const unsigned long long w2 = pk_readlane_u64(pk_f64_bits(inv_sig2 * fin[2]), 0);
+            if (lane == 0) { PK_PROF(3) }
+            // the result line: six granules + {tag, 0}, one store instruction
+            const unsigned v = lane < 6 ? pk_half_of3(w0, w1, w2, lane) : 0u;
+            if (lane < 7) store_sys_u64(&res_host[lane], pk_granule(tag, v));
+            if (lane == 0) { PK_PROF(4) }
+        }
     }
 }
 
+#ifdef FED_PK_PROF
+#include <time.h>
+static inline long long pk_host_ns(void) {
+    struct timespec ts;
+    clock_gettime(CLOCK_MONOTONIC, &ts);
+    return (long long)ts.tv_sec * 1000000000ll + ts.tv_nsec;
+}
+#endif
+
 struct FedPersistentLinear {
-    double* ws = nullptr;          // tickets + slab
-    PersistentState* st = nullptr;
+    unsigned long long* ctl = nullptr;  // broadcast line + partial slots
     double* req = nullptr;         // pinned [seq a b seq_pre]
-    double* res = nullptr;         // pinned [3 results | seq]
+    double* res = nullptr;         // pinned result line (8 words)
     hipStream_t stream = nullptr;
-    unsigned long long seq = 0;
+    unsigned long long seq = 0;    // last sequence sent
     int grid = 512;
+    int relaunches = 0;            // launches after the first one
     // launch parameters (for transparent relaunch after idle self-exit)
     const void* x = nullptr;
     const void* y = nullptr;
@@ -896,19 +1069,25 @@ struct FedPersistentLinear {
     int dtype = FED_BF16;
     void* req_dev = nullptr;
     void* res_dev = nullptr;
+#ifdef FED_PK_PROF
+    unsigned long long* prof = nullptr;  // [grid][8] device stamps
+    long long host_ns[2] = {0, 0};       // request written, result seen
+#endif
 };
 
 // Frees everything start allocated (a null member was never allocated).
 static void persistent_free(FedPersistentLinear* e) {
-    if (e->ws) (void)hipFree(e->ws);
-    if (e->st) (void)hipFree(e->st);
+    if (e->ctl) (void)hipFree(e->ctl);
     if (e->req) (void)hipHostFree(e->req);
     if (e->res) (void)hipHostFree(e->res);
     if (e->stream) (void)hipStreamDestroy(e->stream);
+#ifdef FED_PK_PROF
+    if (e->prof) (void)hipFree(e->prof);
+#endif
     delete e;
 }
 
-// Every block spins on flags that other blocks publish, so the whole grid
+// Every block spins on words that other blocks publish, so the whole grid
 // must be resident at once.  True iff the occupancy query for this dtype's
 // instantiation admits e->grid blocks on the current device.
 static bool persistent_grid_fits(const FedPersistentLinear* e) {
@@ -936,9 +1115,10 @@ static bool persistent_grid_fits(const FedPersistentLinear* e) {
     return (long long)per_cu * cus >= e->grid;
 }
 
-static int persistent_launch(FedPersistentLinear* e) {
-    unsigned* ticket = (unsigned*)e->ws;
-    double* slab = e->ws + 72;
+// (Re)launch the server so that it continues after sequence `served`: first
+// the init kernel (every tag = low 32 bits of `served`, see INIT INVARIANT),
+// then the resident kernel, both on the server's stream.
+static int persistent_launch(FedPersistentLinear* e, unsigned long long served) {
     // Poll protocol A/B on top of the resident shard (same box, 5 reps
     // each, interleaved, default bench arguments): the wave-wide seqlock
     // poll 70.6-75.6k calls/s vs detect-then-read 60.4-64.3k -- one
@@ -949,29 +1129,35 @@ static int persistent_launch(FedPersistentLinear* e) {
     // seqlock poll; FED_PK_SEQLOCK=0 selects the two-step poll.
     const char* sl = getenv("FED_PK_SEQLOCK");
     const int seqlock_on = sl ? (atoi(sl) != 0) : 1;
-    const char* fm = getenv("FED_PK_FENCE");
-    const int fence_mode = fm ? (atoi(fm) != 0) : 1;
+    const long long ctl_words = PK_CTL_WORDS(e->grid);
+    hipLaunchKernelGGL(k_persistent_init, dim3((unsigned)((ctl_words + 255) / 256)), dim3(256), 0,
+                       e->stream, e->ctl, ctl_words, (unsigned long long*)e->res_dev,
+                       (unsigned)served);
+    if (hipGetLastError() != hipSuccess) return -3;
     switch (e->dtype) {
         case FED_BF16:
             hipLaunchKernelGGL(k_gaussian_persistent<bf16_tag>, dim3(e->grid), dim3(256), 0,
                                e->stream, (const bf16_tag*)e->x, (const bf16_tag*)e->y, e->n,
-                               e->inv_sig2, e->logp_const, slab, ticket, e->st,
-                               (const volatile double*)e->req_dev, (double*)e->res_dev,
-                               seqlock_on, fence_mode);
+                               e->inv_sig2, e->logp_const, e->ctl,
+                               (const volatile double*)e->req_dev,
+                               (unsigned long long*)e->res_dev, seqlock_on,
+                               served PK_PROF_ARG(e));
             break;
         case FED_F32:
             hipLaunchKernelGGL(k_gaussian_persistent<float>, dim3(e->grid), dim3(256), 0,
                                e->stream, (const float*)e->x, (const float*)e->y, e->n,
-                               e->inv_sig2, e->logp_const, slab, ticket, e->st,
-                               (const volatile double*)e->req_dev, (double*)e->res_dev,
-                               seqlock_on, fence_mode);
+                               e->inv_sig2, e->logp_const, e->ctl,
+                               (const volatile double*)e->req_dev,
+                               (unsigned long long*)e->res_dev, seqlock_on,
+                               served PK_PROF_ARG(e));
             break;
         case FED_F64:
             hipLaunchKernelGGL(k_gaussian_persistent<double>, dim3(e->grid), dim3(256), 0,
                                e->stream, (const double*)e->x, (const double*)e->y, e->n,
-                               e->inv_sig2, e->logp_const, slab, ticket, e->st,
-                               (const volatile double*)e->req_dev, (double*)e->res_dev,
-                               seqlock_on, fence_mode);
+                               e->inv_sig2, e->logp_const, e->ctl,
+                               (const volatile double*)e->req_dev,
+                               (unsigned long long*)e->res_dev, seqlock_on,
+                               served PK_PROF_ARG(e));
             break;
         default:
             return -2;
@@ -991,13 +1177,12 @@ void* fed_gaussian_persistent_start(
             int g = atoi(env);
             if (g >= 8 && g <= 1024 && (g & (g - 1)) == 0) e->grid = g;
         }
+        // initial host sequence (tests start just below the 32-bit tag wrap)
+        const char* s0 = getenv("FED_PK_SEQ0");
+        if (s0) e->seq = strtoull(s0, nullptr, 10);
     }
-    const long long ws_words = 72 + 3 * (long long)e->grid;
     if (hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&e->ws, ws_words * 8) != hipSuccess ||
-        hipMemset(e->ws, 0, ws_words * 8) != hipSuccess ||
-        hipMalloc(&e->st, sizeof(PersistentState)) != hipSuccess ||
-        hipMemset(e->st, 0, sizeof(PersistentState)) != hipSuccess ||
+        hipMalloc(&e->ctl, PK_CTL_WORDS(e->grid) * 8) != hipSuccess ||
         hipHostMalloc((void**)&e->req, 8 * 8, hipHostMallocMapped) != hipSuccess ||
         hipHostMalloc((void**)&e->res, 8 * 8, hipHostMallocMapped) != hipSuccess) {
         persistent_free(e);
@@ -1007,6 +1192,9 @@ void* fed_gaussian_persistent_start(
         e->req[i] = 0.0;
         e->res[i] = 0.0;
     }
+    // no request pending: seq and seq_pre name the last sequence sent
+    ((unsigned long long*)e->req)[0] = e->seq;
+    ((unsigned long long*)e->req)[3] = e->seq;
     void* req_dev = nullptr;
     void* res_dev = nullptr;
     if (hipHostGetDevicePointer(&req_dev, e->req, 0) != hipSuccess ||
@@ -1022,7 +1210,14 @@ void* fed_gaussian_persistent_start(
     e->logp_const = -0.5 * (double)n * log(2.0 * M_PI * sigma * sigma);
     e->req_dev = req_dev;
     e->res_dev = res_dev;
-    if (!persistent_grid_fits(e) || persistent_launch(e) != 0) {
+#ifdef FED_PK_PROF
+    if (hipMalloc(&e->prof, 8 * 8 * (long long)e->grid) != hipSuccess ||
+        hipMemset(e->prof, 0, 8 * 8 * (long long)e->grid) != hipSuccess) {
+        persistent_free(e);
+        return nullptr;
+    }
+#endif
+    if (!persistent_grid_fits(e) || persistent_launch(e, e->seq) != 0) {
         persistent_free(e);
         return nullptr;
     }
@@ -1032,30 +1227,84 @@ void* fed_gaussian_persistent_start(
 int fed_gaussian_persistent_eval(void* handle, double a, double b, double* out3) {
     FedPersistentLinear* e = (FedPersistentLinear*)handle;
     e->seq += 1;
+    const unsigned tag = (unsigned)e->seq;
+#ifdef FED_PK_PROF
+    e->host_ns[0] = pk_host_ns();
+#endif
     __atomic_store_n((unsigned long long*)&e->req[3], e->seq, __ATOMIC_RELEASE);
     e->req[1] = a;
     e->req[2] = b;
     __atomic_store_n((unsigned long long*)&e->req[0], e->seq, __ATOMIC_RELEASE);
-    volatile unsigned long long* flag = ((volatile unsigned long long*)e->res) + 3;
+    // the result line: aligned 8-byte loads; a value counts only under its
+    // own granules' tags
+    volatile unsigned long long* line = (volatile unsigned long long*)e->res;
     int relaunches = 0;
     for (long long spins = 0; spins < 4000000000LL; ++spins) {
-        if (*flag >= e->seq) {
-            out3[0] = e->res[0];
-            out3[1] = e->res[1];
-            out3[2] = e->res[2];
+        unsigned long long g[6];
+        bool ok = true;
+        for (int k = 0; k < 6; ++k) {
+            g[k] = line[k];
+            ok &= (unsigned)(g[k] >> 32) == tag;
+        }
+        if (ok) {
+#ifdef FED_PK_PROF
+            e->host_ns[1] = pk_host_ns();
+#endif
+            for (int k = 0; k < 3; ++k) {
+                union { unsigned long long u; double d; } c;
+                c.u = (g[2 * k + 1] << 32) | (g[2 * k] & 0xFFFFFFFFull);
+                out3[k] = c.d;
+            }
             return 0;
         }
-        if ((spins & 0xFFFFF) == 0xFFFFF) {  // every ~1M spins (~1-2 ms)
-            // server may have idle-exited (bounded request poll); relaunch --
-            // the fresh kernel sees the pending req_seq and serves it
-            if (hipStreamQuery(e->stream) != hipErrorNotReady) {
+        // seventh word: the server gave up under the tag we wait for (idle
+        // exit racing this request, or a combine timeout) and is exiting
+        const unsigned long long code = line[6];
+        const bool gave_up = (unsigned)(code >> 32) == tag && (unsigned)code != 0u;
+        if (gave_up || (spins & 0xFFFFF) == 0xFFFFF) {  // or every ~1M spins (~1-2 ms)
+            if (gave_up) {
+                if (hipStreamSynchronize(e->stream) != hipSuccess) return -7;
+                line[6] = ((unsigned long long)(tag - 1u)) << 32;  // consumed
+            }
+            // server may have idle-exited (bounded request poll); relaunch at
+            // the last served sequence -- the fresh kernel sees the pending
+            // request and serves it exactly once
+            if (gave_up || hipStreamQuery(e->stream) != hipErrorNotReady) {
                 if (relaunches++ > 4) return -6;
-                if (persistent_launch(e) != 0) return -7;
+                e->relaunches += 1;
+                if (persistent_launch(e, e->seq - 1) != 0) return -7;
             }
         }
     }
     return -6;
 }
+
+// launches of the server after the first one (idle exits that were followed
+// by a call)
+int fed_gaussian_persistent_relaunch_count(void* handle) {
+    return ((FedPersistentLinear*)handle)->relaunches;
+}
+
+#ifdef FED_PK_PROF
+// Copies out the stamps of the last served call ([grid][8] clock words) and
+// the host's two timestamps (ns); call it while the server is idle.  The
+// copy runs on a stream of its own: the resident kernel occupies e->stream.
+int fed_gaussian_persistent_prof(
+    void* handle, unsigned long long* stamps, long long cap_words, long long* host_ns2
+) {
+    FedPersistentLinear* e = (FedPersistentLinear*)handle;
+    const long long words = 8 * (long long)e->grid;
+    if (cap_words < words) return -2;
+    hipStream_t cs = nullptr;
+    if (hipStreamCreateWithFlags(&cs, hipStreamNonBlocking) != hipSuccess) return -3;
+    hipError_t err = hipMemcpyAsync(stamps, e->prof, words * 8, hipMemcpyDeviceToHost, cs);
+    if (err == hipSuccess) err = hipStreamSynchronize(cs);
+    (void)hipStreamDestroy(cs);
+    host_ns2[0] = e->host_ns[0];
+    host_ns2[1] = e->host_ns[1];
+    return err == hipSuccess ? e->grid : (int)err;
+}
+#endif
 
 int fed_gaussian_persistent_debug(void* handle, double* req8, double* res8) {
     FedPersistentLinear* e = (FedPersistentLinear*)handle;
