@@ -1,0 +1,358 @@
+"""Poisson and Gaussian GLM logp+grad models on the row-group fused kernel.
+
+Parameters ``beta[K]``, private shard ``X[N,K]``, ``y[N]`` and the linear
+predictor ``z = X @ beta (+ offset)``:
+
+Poisson regression (log link, optional exposure ``offset = log(exposure)``)
+
+    logp = sum( y*z - exp(z) ) - sum( lgamma(y+1) )
+    grad = X^T @ (y - exp(z))
+
+Gaussian regression on K covariates (identity link, fixed ``sigma``)
+
+    r    = y - z
+    logp = -N/2 * log(2*pi*sigma^2) - sum(r^2) / (2*sigma^2)
+    grad = X^T @ r / sigma^2
+
+Compute paths:
+* eager torch (CPU, ``use_kernels=False``, shapes the kernel does not
+  cover): a matmul each way + elementwise; fp64 data -> fp64 math,
+  otherwise fp32 with fp64 row sums;
+* MI355X: ONE fused CDNA4 HIP kernel (``ops.glm_family_logp_grad``,
+  csrc/glm_family.hip) reading X exactly once.  A group of G <= 64 lanes
+  owns a row, so a narrow model is read at its own size: the feature dim is
+  zero-padded only to the next power-of-two multiple of one 16-byte vector
+  (8 bf16 / 4 f32), K = 20 -> 32, not to a whole wave.  ``y`` and
+  ``offset`` are kept in f32 whatever the dtype of X (counts above 256 do
+  not survive bf16).  The beta-independent part of logp is added on the
+  device.
+
+Overflow: the fp32 paths (the kernel, and eager on bf16/f32 data) form
+``exp(z)`` in fp32.  For a row with ``z > 88`` that is ``inf``, so the
+Poisson ``logp`` is ``-inf`` and the gradient is not finite, in both paths
+alike.  Only fp64 data evaluated eagerly goes further (to ``z ~ 709``).
+Counts are exact in f32 up to 2^24.
+"""
+from __future__ import annotations
+
+import math
+from typing import List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from .base import LogpGradModel
+
+__all__ = [
+    "PoissonGLMModel",
+    "GaussianGLMModel",
+    "generate_poisson_dataset",
+    "generate_gaussian_glm_dataset",
+]
+
+
+def generate_poisson_dataset(
+    n_rows: int,
+    n_features: int,
+    *,
+    seed: int = 0,
+    beta_scale: float = 0.5,
+    exposure: bool = True,
+) -> Tuple[np.ndarray, np.ndarray, Optional[np.ndarray], np.ndarray]:
+    """Synthetic (X, y, offset, beta_true) count data.
+
+    ``X[:, 0] = 1`` (intercept), the other columns are standard normal over
+    sqrt(K), so ``z`` stays of order ``beta_scale``.  With ``exposure`` each
+    row gets an exposure in [0.5, 2] and ``offset = log(exposure)``;
+    otherwise ``offset`` is ``None``.
+    """
+    rng = np.random.RandomState(seed)
+    X = rng.standard_normal((n_rows, n_features)) / np.sqrt(n_features)
+    X[:, 0] = 1.0
+    beta = rng.standard_normal(n_features) * beta_scale
+    offset = np.log(rng.uniform(0.5, 2.0, size=n_rows)) if exposure else None
+    z = X @ beta + (offset if exposure else 0.0)
+    y = rng.poisson(np.exp(z)).astype(np.float64)
+    return X, y, offset, beta
+
+
+def generate_gaussian_glm_dataset(
+    n_rows: int,
+    n_features: int,
+    *,
+    sigma: float = 0.5,
+    seed: int = 0,
+    beta_scale: float = 0.5,
+) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Synthetic (X, y, beta_true) with ``y ~ N(X @ beta, sigma^2)``."""
+    rng = np.random.RandomState(seed)
+    X = rng.standard_normal((n_rows, n_features)) / np.sqrt(n_features)
+    X[:, 0] = 1.0
+    beta = rng.standard_normal(n_features) * beta_scale
+    y = X @ beta + sigma * rng.standard_normal(n_rows)
+    return X, y, beta
+
+
+def _as_tensor(a) -> torch.Tensor:
+    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+
+
+class _GLMFamilyModel(LogpGradModel):
+    """What the families share: the shard, zero-column padding to a kernel
+    size, the kernel/eager dispatch and the ``out=`` seam.  A family names
+    its ``_link`` and gives ``_terms`` (the eager per-row logp term and
+    residual) and ``_logp_const``."""
+
+    param_names = ("beta",)
+    _link: str = ""
+
+    def __init__(
+        self,
+        X,
+        y,
+        *,
+        offset=None,
+        device=None,
+        dtype: torch.dtype = None,
+        use_kernels: Optional[bool] = None,
+        delay: Optional[float] = None,
+    ) -> None:
+        super().__init__(delay=delay)
+        X, y = _as_tensor(X), _as_tensor(y)
+        if X.dim() != 2 or y.dim() != 1 or X.shape[0] != y.shape[0]:
+            raise ValueError("X must be [N,K] and y [N].")
+        if X.shape[1] < 1:
+            raise ValueError("X must have at least one column.")
+        if offset is not None:
+            offset = _as_tensor(offset)
+            if offset.shape != y.shape:
+                raise ValueError("offset must be [N].")
+        if dtype is None:
+            dtype = X.dtype if X.is_floating_point() else torch.float64
+        if device is None:
+            device = X.device
+        # y and offset: f32 (what the kernel reads) unless the shard is fp64
+        self._acc_dtype = torch.float64 if dtype == torch.float64 else torch.float32
+        self._X = X.to(device=device, dtype=dtype).contiguous()
+        self._y = y.to(device=device, dtype=self._acc_dtype).contiguous()
+        self._offset = (
+            None if offset is None
+            else offset.to(device=device, dtype=self._acc_dtype).contiguous()
+        )
+        self._use_kernels = use_kernels
+        self._n, self._k = self._X.shape
+        self._k_pad = 0
+        if (use_kernels is None or use_kernels) and self._X.is_cuda:
+            from ..ops import glm_family_padded_k
+
+            # pad the feature dim to the next size the kernel is compiled
+            # for; zero columns change nothing: z is unaffected and their
+            # gradient is exactly 0.
+            k_eff = glm_family_padded_k(dtype, self._k)
+            if k_eff is not None and k_eff != self._k:
+                self._k_pad = k_eff - self._k
+                pad = torch.zeros(
+                    (self._n, self._k_pad), device=self._X.device, dtype=self._X.dtype
+                )
+                self._X = torch.cat([self._X, pad], dim=1).contiguous()
+
+    # -- what a family provides -------------------------------------------
+    def _terms(self, y: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(per-row logp term, residual d term / d z), shaped like ``z``."""
+        raise NotImplementedError
+
+    _logp_const: float = 0.0
+    _sigma: float = 1.0
+
+    # -- shared -------------------------------------------------------------
+    @property
+    def device(self):
+        return self._X.device
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._n)
+
+    @property
+    def n_features(self) -> int:
+        return int(self._k)
+
+    @property
+    def _k_eff(self) -> int:
+        """Feature dim as the kernel sees it (incl. zero padding)."""
+        return self._k + self._k_pad
+
+    @property
+    def fused_size(self) -> int:
+        """Layout of the fused fp64 output buffer: [logp, grad[K]]."""
+        return 1 + int(self._k)
+
+    def _kernel_path(self) -> bool:
+        want = self._X.is_cuda if self._use_kernels is None else self._use_kernels
+        if want and self._use_kernels is None:
+            from ..ops import glm_family_kernel_supports
+
+            if not glm_family_kernel_supports(self._X.dtype, self._k_eff):
+                import warnings
+
+                warnings.warn(
+                    f"fused GLM family kernel not compiled for (dtype={self._X.dtype}, "
+                    f"K={self._k_eff}); using the eager two-matmul path (~2x slower). "
+                    f"Supported: bf16 up to K=2048, f32 up to K=1024.",
+                    stacklevel=3,
+                )
+                return False
+        return want
+
+    def logp_grad(
+        self, beta, out: Optional[torch.Tensor] = None
+    ) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        """``out`` (fp64[1+K], same device) receives the fused [logp, grad]
+        in place -- the zero-copy seam to the RCCL all-reduce buffer."""
+        beta = torch.as_tensor(beta)
+        if beta.shape != (self._k,):
+            raise ValueError(f"beta must have shape ({self._k},), got {tuple(beta.shape)}.")
+        if self._kernel_path():
+            from ..ops import glm_family_logp_grad
+
+            kw = dict(
+                link=self._link, offset=self._offset, sigma=self._sigma,
+                logp_const=self._logp_const,
+            )
+            if self._k_pad:
+                beta = torch.cat(
+                    [beta.to(torch.float32),
+                     torch.zeros(self._k_pad, dtype=torch.float32, device=beta.device)]
+                )
+                # ``out`` (if given) is sized [1 + k]; the kernel writes
+                # [1 + k_eff] -- evaluate into the kernel's own buffer and
+                # copy the un-padded slice over.
+                logp, grad = glm_family_logp_grad(self._X, self._y, beta, **kw)
+                grad = grad[: self._k]
+                if out is not None:
+                    out[0] = logp
+                    out[1:] = grad
+                    return out[0], [out[1:]]
+                return logp, [grad]
+            logp, grad = glm_family_logp_grad(self._X, self._y, beta, out=out, **kw)
+            return logp, [grad]
+        logp, grads = self._logp_grad_eager(beta)
+        if out is not None:
+            out[0] = logp
+            out[1:] = grads[0]
+            return out[0], [out[1:]]
+        return logp, grads
+
+    def _logp_grad_eager(self, beta: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
+        logp, G = self._logp_grad_batched_eager(beta.reshape(self._k, 1))
+        return logp[0], [G[:, 0]]
+
+    def logp_grad_batched(self, theta) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Evaluate B chains at once: theta[K,B] -> (logp[B], G[K,B]), by
+        eager torch on every device (the MFMA batched kernels cover the
+        logistic family only)."""
+        theta = torch.as_tensor(theta)
+        if theta.dim() != 2 or theta.shape[0] != self._k:
+            raise ValueError(f"theta must be [{self._k}, B], got {tuple(theta.shape)}")
+        return self._logp_grad_batched_eager(theta)
+
+    def _logp_grad_batched_eager(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        X = self._X[:, : self._k]
+        acc = self._acc_dtype
+        theta = theta.to(device=X.device, dtype=acc)
+        B = theta.shape[1]
+        logp = torch.full((B,), self._logp_const, dtype=torch.float64, device=X.device)
+        G = torch.zeros((self._k, B), dtype=torch.float64, device=X.device)
+        # large GPU shard in a narrow type: chunk the rows so the upcast of
+        # X stays O(chunk) instead of a second copy of a multi-GB shard
+        chunked = X.dtype != acc and X.is_cuda and self._n > 1 << 20
+        step = 1 << 21 if chunked else max(self._n, 1)
+        for s in range(0, self._n, step):
+            Xf = X[s : s + step].to(acc)
+            Z = Xf @ theta
+            if self._offset is not None:
+                Z = Z + self._offset[s : s + step, None]
+            term, resid = self._terms(self._y[s : s + step, None], Z)
+            logp += torch.sum(term, dim=0, dtype=torch.float64)
+            G += (Xf.t() @ resid).to(torch.float64)
+        return logp, G
+
+
+class PoissonGLMModel(_GLMFamilyModel):
+    """Federated worker model: Poisson regression (log link) on a private
+    shard of counts, with an optional exposure offset."""
+
+    _link = "poisson"
+
+    def __init__(
+        self,
+        X,
+        y,
+        *,
+        offset=None,
+        device=None,
+        dtype: torch.dtype = None,
+        use_kernels: Optional[bool] = None,
+        delay: Optional[float] = None,
+    ) -> None:
+        """
+        Parameters
+        ----------
+        X, y : array-like
+            ``X[N,K]`` covariates and ``y[N]`` non-negative integer counts.
+        offset : array-like, optional
+            ``offset[N]`` added to ``X @ beta`` (``log(exposure)``).
+        device, dtype, use_kernels, delay
+            As for :class:`LogisticGLMModel`; ``dtype`` is the storage type
+            of ``X`` only.
+        """
+        y64 = _as_tensor(y).detach().to(device="cpu", dtype=torch.float64)
+        if y64.dim() == 1 and y64.numel():
+            if not bool(torch.all(torch.isfinite(y64))):
+                raise ValueError("Poisson y must be finite.")
+            if bool(torch.any(y64 < 0)) or bool(torch.any(y64 != torch.floor(y64))):
+                raise ValueError("Poisson y must hold non-negative integer counts.")
+        super().__init__(
+            X, y, offset=offset, device=device, dtype=dtype, use_kernels=use_kernels,
+            delay=delay,
+        )
+        # the beta-independent part of logp, once, in fp64
+        self._logp_const = -float(torch.sum(torch.lgamma(y64 + 1.0)))
+
+    def _terms(self, y, z):
+        mu = torch.exp(z)
+        return y * z - mu, y - mu
+
+
+class GaussianGLMModel(_GLMFamilyModel):
+    """Federated worker model: Gaussian regression on K covariates
+    (identity link, fixed noise scale) on a private shard."""
+
+    _link = "gaussian"
+
+    def __init__(
+        self,
+        X,
+        y,
+        sigma: float,
+        *,
+        offset=None,
+        device=None,
+        dtype: torch.dtype = None,
+        use_kernels: Optional[bool] = None,
+        delay: Optional[float] = None,
+    ) -> None:
+        sigma = float(sigma)
+        if not (sigma > 0.0 and math.isfinite(sigma)):
+            raise ValueError("sigma must be positive and finite.")
+        super().__init__(
+            X, y, offset=offset, device=device, dtype=dtype, use_kernels=use_kernels,
+            delay=delay,
+        )
+        self._sigma = sigma
+        self._logp_const = -0.5 * self._n * math.log(2.0 * math.pi * sigma * sigma)
+
+    def _terms(self, y, z):
+        r = y - z
+        sig2 = self._sigma * self._sigma
+        return -(r * r) * (0.5 / sig2), r * (1.0 / sig2)

@@ -23,6 +23,9 @@ __all__ = [
     "gaussian_linear_logp_grad",
     "gaussian_linear_eval_sync",
     "logistic_glm_logp_grad",
+    "glm_family_logp_grad",
+    "glm_family_padded_k",
+    "glm_family_kernel_supports",
     "ode_poly_logp_grad",
 ]
 
@@ -89,6 +92,14 @@ def _try_load() -> Optional[ctypes.CDLL]:
     lib.fed_logistic_glm.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+        ctypes.c_int, ctypes.c_void_p,
+    ]
+    lib.fed_glm_family.restype = ctypes.c_int
+    lib.fed_glm_family.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_double, ctypes.c_double,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
         ctypes.c_int, ctypes.c_void_p,
     ]
     lib.fed_ode_lv_eval.restype = ctypes.c_int
@@ -585,4 +596,96 @@ def logistic_glm_logp_grad(
         ws.numel() * 4, _DTYPE_CODE[X.dtype], _stream_ptr(),
     )
     _check(rc, "fed_logistic_glm")
+    return out[0], out[1:]
+
+
+#: link codes of fed_glm_family (csrc/glm_family.hip)
+GLM_FAMILY_LINKS = {"poisson": 0, "gaussian": 1, "logistic": 2}
+_GLM_FAMILY_VEC = {torch.bfloat16: 8, torch.float32: 4}
+#: lanes per row the family kernel is compiled for: G = 1..64 lanes of one
+#: 16-byte vector each, then 2 and 4 column chunks of a whole wave
+_GLM_FAMILY_LANES = (1, 2, 4, 8, 16, 32, 64, 128, 256)
+
+
+def glm_family_padded_k(dtype, K: int) -> Optional[int]:
+    """Smallest feature count >= K the family kernel is compiled for at
+    ``dtype`` (bf16: 8, 16, ..., 2048; f32: 4, 8, ..., 1024), or ``None``
+    when K is above the maximum or the dtype is not supported."""
+    vec = _GLM_FAMILY_VEC.get(dtype)
+    K = int(K)
+    if vec is None or K < 1:
+        return None
+    for lanes in _GLM_FAMILY_LANES:
+        if lanes * vec >= K:
+            return lanes * vec
+    return None
+
+
+def glm_family_kernel_supports(dtype, K: int) -> bool:
+    return glm_family_padded_k(dtype, K) == int(K)
+
+
+def glm_family_logp_grad(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    beta: torch.Tensor,
+    *,
+    link: str,
+    offset: Optional[torch.Tensor] = None,
+    sigma: float = 1.0,
+    logp_const: float = 0.0,
+    out: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Fused GLM logp+grad on the row-group kernel; X read once.
+
+    ``link`` is ``"poisson"`` (log link: ``y*z - exp(z)``), ``"gaussian"``
+    (identity: ``-(y-z)^2 / (2 sigma^2)``) or ``"logistic"``, with
+    ``z = X @ beta (+ offset)``.  ``X[N,K]`` is bf16 or f32 with K one of
+    the sizes of :func:`glm_family_padded_k`; ``y`` and ``offset`` are
+    f32[N].  ``logp_const`` (the beta-independent part of logp) is added on
+    the device, so the result is final without a further launch.  Returns
+    (logp, grad[K]) as fp64 views of ``out``.
+    """
+    lib = require_kernels()
+    if link not in GLM_FAMILY_LINKS:
+        raise ValueError(f"unknown link {link!r}; expected one of {sorted(GLM_FAMILY_LINKS)}")
+    n, K = X.shape
+    if X.dtype not in _GLM_FAMILY_VEC:
+        raise TypeError(f"unsupported dtype {X.dtype}")
+    if not glm_family_kernel_supports(X.dtype, K):
+        raise ValueError(f"family kernel not compiled for (dtype={X.dtype}, K={K})")
+    if not X.is_cuda:
+        raise ValueError("X must be on a ROCm device")
+    if y.dtype != torch.float32 or y.shape != (n,) or y.device != X.device:
+        raise ValueError("y must be f32[N] on X's device")
+    if offset is not None and (
+        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
+    ):
+        raise ValueError("offset must be f32[N] on X's device")
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+    _require_contiguous(X=X, y=y)
+    if offset is not None:
+        _require_contiguous(offset=offset)
+    if X.data_ptr() % 16:
+        raise ValueError("X must be 16-byte aligned")
+    beta_f32 = beta.detach().to(device=X.device, dtype=torch.float32).contiguous()
+    if beta_f32.shape != (K,):
+        raise ValueError(f"beta must have shape ({K},), got {tuple(beta_f32.shape)}")
+    if out is None:
+        out = torch.empty(1 + K, dtype=torch.float64, device=X.device)
+    elif (
+        out.dtype != torch.float64 or out.shape != (1 + K,) or out.device != X.device
+        or not out.is_contiguous()
+    ):
+        raise ValueError(f"out must be a contiguous fp64[{1 + K}] on X's device")
+    ws = _workspace(X.device, f"glm_family{K}", 1024 * K, dtype=torch.float32)
+    rc = lib.fed_glm_family(
+        X.data_ptr(), y.data_ptr(), offset.data_ptr() if offset is not None else None,
+        n, K, beta_f32.data_ptr(), GLM_FAMILY_LINKS[link],
+        float(sigma), float(logp_const),
+        out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+        _DTYPE_CODE[X.dtype], _stream_ptr(),
+    )
+    _check(rc, "fed_glm_family")
     return out[0], out[1:]

@@ -25,6 +25,8 @@
 //   glm_gaussian.hip          fused Gaussian kernel, shard engine, server
 //   glm_logistic.hip          single-chain logistic kernel
 //   glm_logistic_batched.hip  16-chain MFMA logistic kernels
+//   glm_family.hip            row-group single-chain kernel, link as a policy
+//                             (Poisson, Gaussian on K covariates, logistic)
 
 #pragma once
 
