@@ -7,6 +7,10 @@ bytes and effective bandwidth; one JSON line per config.
 (b) Logistic link at K = 100 (zero-padded to 128) against the existing
     wave-per-row ``logistic_glm_logp_grad`` on the same data padded to 512.
 (c) Both kernels at K = 512 (the same layout in both).
+(d) 16 chains, Poisson and Gaussian, bf16, K in {16, 128, 512, 1024}: the
+    MFMA batched kernel (``logp_grad_batched``'s kernel path) against the
+    eager batched path and against 16 back-to-back single-chain kernel
+    calls, the three alternating in one process.
 
 Times are device events around ``--inner`` back-to-back evaluations, after
 ``--warmup`` untimed ones.  In (b) and (c) the two kernels alternate in one
@@ -26,7 +30,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import numpy as np
 import torch
 
-from pytensor_federated_amd.models import PoissonGLMModel
+from pytensor_federated_amd.models import GaussianGLMModel, PoissonGLMModel
 from pytensor_federated_amd.ops import glm_family_logp_grad, logistic_glm_logp_grad
 
 DEV = "cuda:0"
@@ -130,6 +134,56 @@ def family_vs_wave_per_row(n, K, k_family, k_wave, label, args):
     }
 
 
+def batched_vs_eager_vs_single(n, K, family, args):
+    gen = torch.Generator(device=DEV).manual_seed(3000 + K)
+    X = random_X(n, K, K, gen)
+    beta = torch.randn(K, device=DEV, generator=gen) * 0.5
+    scales = torch.linspace(-1.0, 1.0, 16, device=DEV)
+    theta = (beta[:, None] * scales[None, :]).contiguous()
+    if family == "poisson":
+        offset = torch.log(torch.rand(n, device=DEV, generator=gen) * 1.5 + 0.5)
+        y = torch.poisson(torch.exp(X.float() @ beta + offset), generator=gen)
+        m = PoissonGLMModel(X, y, offset=offset, use_kernels=True)
+        nbytes = n * K * 2 + 2 * n * 4
+    else:
+        y = X.float() @ beta + 0.5 * torch.randn(n, device=DEV, generator=gen)
+        m = GaussianGLMModel(X, y, 0.5, use_kernels=True)
+        nbytes = n * K * 2 + n * 4
+    assert m._batched_kernel_path() and m._k_pad == 0
+    out1 = torch.empty(1 + K, dtype=torch.float64, device=DEV)
+    cols = [theta[:, b].contiguous() for b in range(16)]
+
+    def single16():
+        for b in range(16):
+            m.logp_grad(cols[b], out=out1)
+
+    steps = max(args.steps // 3, 5)
+    ms_k, ms_e, ms_s = device_ms(
+        [lambda: m._logp_grad_batched_kernel(theta),
+         lambda: m._logp_grad_batched_eager(theta), single16],
+        steps, args.warmup, max(args.inner // 2, 1),
+    )
+    logp_k, G_k = m._logp_grad_batched_kernel(theta)
+    logp_e, G_e = m._logp_grad_batched_eager(theta)
+    single = [m.logp_grad(cols[b]) for b in range(16)]
+    logp_s = torch.stack([s[0] for s in single])
+    G_s = torch.stack([s[1][0] for s in single], dim=1)
+    torch.cuda.synchronize()
+    return {
+        "config": "d", "link": family, "dtype": "bf16", "rows": n, "K": K, "chains": 16,
+        "batched_kernel": summary(ms_k, nbytes),
+        "eager_batched": summary(ms_e, nbytes),
+        "single_chain_x16": summary(ms_s, 16 * nbytes),
+        "eager_over_kernel": float(np.median(ms_e) / np.median(ms_k)),
+        "single_x16_over_kernel": float(np.median(ms_s) / np.median(ms_k)),
+        "logp_max_rel_diff_vs_eager": float(((logp_k - logp_e) / logp_e).abs().max()),
+        "logp_max_rel_diff_vs_single": float(((logp_k - logp_s) / logp_s).abs().max()),
+        "grad_max_abs_diff_vs_eager": float((G_k - G_e).abs().max()),
+        "grad_max_abs_diff_vs_single": float((G_k - G_s).abs().max()),
+        "grad_max_abs": float(G_s.abs().max()),
+    }
+
+
 def main():
     parser = argparse.ArgumentParser()
     parser.add_argument("--rows", type=int, default=2_000_000)
@@ -137,6 +191,8 @@ def main():
     parser.add_argument("--warmup", type=int, default=5)
     parser.add_argument("--inner", type=int, default=4)
     parser.add_argument("--configs", default="a,b,c")
+    parser.add_argument("--batched-k", default="16,128,512,1024",
+                        help="feature counts of config d")
     args = parser.parse_args()
     assert torch.cuda.is_available(), "needs a ROCm GPU"
     configs = args.configs.split(",")
@@ -147,6 +203,11 @@ def main():
         print(json.dumps(family_vs_wave_per_row(args.rows, 100, 128, 512, "b", args)), flush=True)
     if "c" in configs:
         print(json.dumps(family_vs_wave_per_row(args.rows, 512, 512, 512, "c", args)), flush=True)
+    if "d" in configs:
+        for family in ("poisson", "gaussian"):
+            for K in (int(k) for k in args.batched_k.split(",")):
+                print(json.dumps(batched_vs_eager_vs_single(args.rows, K, family, args)),
+                      flush=True)
 
 
 if __name__ == "__main__":

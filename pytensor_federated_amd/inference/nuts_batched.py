@@ -5,7 +5,8 @@ C independent NUTS chains (same math as :mod:`nuts` -- Hoffman & Gelman
 together: every "round" gathers the ONE pending gradient request of each
 chain into a single batched call ``theta[K, C] -> (logp[C], grad[K, C])``.
 On an MI355X shard that is one batched-kernel sweep for all chains
-(``LogisticGLMModel.logp_grad_batched`` / ``ODEModel.logp_grad_batched``),
+(``logp_grad_batched`` of ``LogisticGLMModel``, ``PoissonGLMModel``,
+``GaussianGLMModel`` and ``ODEModel``),
 so C chains cost close to one.
 
 Mechanically each chain's transition is written as a *generator* that

@@ -26,6 +26,10 @@ Compute paths:
   ``offset`` are kept in f32 whatever the dtype of X (counts above 256 do
   not survive bf16).  The beta-independent part of logp is added on the
   device.
+* MI355X, several chains (``logp_grad_batched``): bf16 shards go 16 chains
+  at a time through the MFMA kernel ``ops.glm_family_logp_grad_batched``
+  (csrc/glm_family_batched.hip), one pass over X for all 16; theta and the
+  residual travel as three bf16 pieces each, so nothing is rounded to bf16.
 
 Overflow: the fp32 paths (the kernel, and eager on bf16/f32 data) form
 ``exp(z)`` in fp32.  For a row with ``z > 88`` that is ``inf``, so the
@@ -248,13 +252,63 @@ class _GLMFamilyModel(LogpGradModel):
         return logp[0], [G[:, 0]]
 
     def logp_grad_batched(self, theta) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Evaluate B chains at once: theta[K,B] -> (logp[B], G[K,B]), by
-        eager torch on every device (the MFMA batched kernels cover the
-        logistic family only)."""
+        """Evaluate B chains at once: theta[K,B] -> (logp[B], G[K,B]).
+
+        On the kernel path with a bf16 shard whose padded K is one of
+        ``ops.GLM_FAMILY_BATCHED_K`` (up to 1024) the chains go through the
+        MFMA batched family kernel in groups of 16, the last group padded
+        with zero columns; theta and the residual are carried as three bf16
+        pieces each, so the result is as accurate as ``logp_grad``'s.
+        Everything else is eager torch: CPU, ``use_kernels=False``, f32 and
+        f64 shards (gfx950's f32-input MFMA runs at 1/16 of the bf16 rate
+        and there is no xf32), and a padded K of 2048, which warns."""
         theta = torch.as_tensor(theta)
         if theta.dim() != 2 or theta.shape[0] != self._k:
             raise ValueError(f"theta must be [{self._k}, B], got {tuple(theta.shape)}")
+        if self._batched_kernel_path():
+            return self._logp_grad_batched_kernel(theta)
         return self._logp_grad_batched_eager(theta)
+
+    def _batched_kernel_path(self) -> bool:
+        if self._X.dtype != torch.bfloat16 or not self._kernel_path():
+            return False
+        from ..ops import glm_family_batched_supports
+
+        if not glm_family_batched_supports(self._X.dtype, self._k_eff):
+            import warnings
+
+            warnings.warn(
+                f"batched GLM family kernel not compiled for K={self._k_eff}; "
+                f"using the eager batched path. Supported: bf16 up to K=1024.",
+                stacklevel=3,
+            )
+            return False
+        return True
+
+    def _logp_grad_batched_kernel(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        from ..ops import BATCH_CHAINS, glm_family_logp_grad_batched
+
+        dev = self._X.device
+        B = theta.shape[1]
+        kw = dict(link=self._link, offset=self._offset, sigma=self._sigma,
+                  logp_const=self._logp_const)
+        if B == BATCH_CHAINS and not self._k_pad:
+            # the samplers' shape: nothing to pad, slice or copy
+            return glm_family_logp_grad_batched(self._X, self._y, theta, **kw)
+        groups = -(-B // BATCH_CHAINS)
+        # padded feature rows and padded chains are zero columns / rows of theta
+        th = torch.zeros(
+            (self._k_eff, groups * BATCH_CHAINS), dtype=torch.float32, device=dev
+        )
+        th[: self._k, :B] = theta.to(device=dev, dtype=torch.float32)
+        logp = torch.empty(groups * BATCH_CHAINS, dtype=torch.float64, device=dev)
+        G = torch.empty((self._k, groups * BATCH_CHAINS), dtype=torch.float64, device=dev)
+        for g in range(groups):
+            cols = slice(g * BATCH_CHAINS, (g + 1) * BATCH_CHAINS)
+            lg, Gg = glm_family_logp_grad_batched(self._X, self._y, th[:, cols], **kw)
+            logp[cols] = lg
+            G[:, cols] = Gg[: self._k]
+        return logp[:B], G[:, :B]
 
     def _logp_grad_batched_eager(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         X = self._X[:, : self._k]

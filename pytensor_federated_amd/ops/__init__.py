@@ -26,6 +26,10 @@ __all__ = [
     "glm_family_logp_grad",
     "glm_family_padded_k",
     "glm_family_kernel_supports",
+    "split_bf16x3",
+    "GLM_FAMILY_BATCHED_K",
+    "glm_family_batched_supports",
+    "glm_family_logp_grad_batched",
     "ode_poly_logp_grad",
 ]
 
@@ -101,6 +105,14 @@ def _try_load() -> Optional[ctypes.CDLL]:
         ctypes.c_double, ctypes.c_double,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
         ctypes.c_int, ctypes.c_void_p,
+    ]
+    lib.fed_glm_family_batched.restype = ctypes.c_int
+    lib.fed_glm_family_batched.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+        ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
+        ctypes.c_double, ctypes.c_double,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+        ctypes.c_void_p,
     ]
     lib.fed_ode_lv_eval.restype = ctypes.c_int
     lib.fed_ode_lv_eval.argtypes = [
@@ -689,3 +701,108 @@ def glm_family_logp_grad(
     )
     _check(rc, "fed_glm_family")
     return out[0], out[1:]
+
+
+def split_bf16x3(theta: torch.Tensor) -> torch.Tensor:
+    """Split ``theta[K, B]`` into three bf16 pieces, transposed: ``[3, B, K]``.
+
+    ``p0 = bf16(theta)``, ``p1 = bf16(theta - p0)``, ``p2 = bf16(theta - p0 -
+    p1)``, the differences taken in f32.  Each difference is exact and drops
+    at least 8 leading bits, so the three pieces sum to any finite f32 whose
+    last bit is above bf16's subnormal range exactly -- what lets the MFMA
+    batched family kernel take bf16 operands without rounding theta.  Pure
+    torch; runs on any device.
+    """
+    rem = theta.detach().to(torch.float32).t().contiguous()
+    pieces = []
+    for i in range(3):
+        p = rem.to(torch.bfloat16)
+        pieces.append(p)
+        if i < 2:
+            rem = rem - p.to(torch.float32)
+    return torch.stack(pieces)
+
+
+#: feature counts the batched family kernel is compiled for: every padded K
+#: the GLM family models produce up to 1024 (at 2048 a block's f32
+#: accumulators alone would be 128 registers per lane)
+GLM_FAMILY_BATCHED_K = (8, 16, 32, 64, 128, 256, 512, 1024)
+#: links of fed_glm_family_batched (the logistic models keep their own kernels)
+_GLM_FAMILY_BATCHED_LINKS = ("poisson", "gaussian")
+#: fp32 slab workspace: the largest grid of any K times its slab rows
+_GLM_FAMILY_BATCHED_WS = 8 << 20
+
+
+def glm_family_batched_supports(dtype, K: int) -> bool:
+    """True for bf16 shards with K in :data:`GLM_FAMILY_BATCHED_K`."""
+    return dtype == torch.bfloat16 and int(K) in GLM_FAMILY_BATCHED_K
+
+
+def glm_family_logp_grad_batched(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    theta: torch.Tensor,
+    *,
+    link: str,
+    offset: Optional[torch.Tensor] = None,
+    sigma: float = 1.0,
+    logp_const: float = 0.0,
+    out: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """16 chains of a Poisson or Gaussian GLM in one pass over X, on the
+    matrix cores (csrc/glm_family_batched.hip): ``theta[K,16]`` ->
+    ``(logp[16], G[K,16])`` as fp64 views of ``out`` (fp64[16 + K*16]).
+
+    ``X[N,K]`` is bf16 with K in :data:`GLM_FAMILY_BATCHED_K`; ``y`` and
+    ``offset`` are f32[N].  theta is handed to the kernel as the three bf16
+    pieces of :func:`split_bf16x3` and the residual is split the same way on
+    the device, so no operand is rounded: the result is as accurate as the
+    single-chain kernel's.  f32 shards are not covered: gfx950's f32-input
+    MFMA runs at 1/16 of the bf16 rate and there is no xf32 format.
+    ``logp_const`` is added to every chain on the device.
+    """
+    lib = require_kernels()
+    if link not in _GLM_FAMILY_BATCHED_LINKS:
+        raise ValueError(
+            f"unknown link {link!r}; expected one of {sorted(_GLM_FAMILY_BATCHED_LINKS)}"
+        )
+    n, K = X.shape
+    B = BATCH_CHAINS
+    if X.dtype != torch.bfloat16:
+        raise TypeError(f"unsupported dtype {X.dtype}: the batched family kernel reads bf16 X")
+    if not glm_family_batched_supports(X.dtype, K):
+        raise ValueError(f"batched family kernel not compiled for (dtype={X.dtype}, K={K})")
+    if not X.is_cuda:
+        raise ValueError("X must be on a ROCm device")
+    if y.dtype != torch.float32 or y.shape != (n,) or y.device != X.device:
+        raise ValueError("y must be f32[N] on X's device")
+    if offset is not None and (
+        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
+    ):
+        raise ValueError("offset must be f32[N] on X's device")
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+    _require_contiguous(X=X, y=y)
+    if offset is not None:
+        _require_contiguous(offset=offset)
+    if X.data_ptr() % 16:
+        raise ValueError("X must be 16-byte aligned")
+    if tuple(theta.shape) != (K, B):
+        raise ValueError(f"theta must be [{K}, {B}], got {tuple(theta.shape)}")
+    pieces = split_bf16x3(theta.to(device=X.device))
+    if out is None:
+        out = torch.empty(B + K * B, dtype=torch.float64, device=X.device)
+    elif (
+        out.dtype != torch.float64 or out.shape != (B + K * B,) or out.device != X.device
+        or not out.is_contiguous()
+    ):
+        raise ValueError(f"out must be a contiguous fp64[{B + K * B}] on X's device")
+    ws = _workspace(X.device, "glm_family_batched", _GLM_FAMILY_BATCHED_WS, dtype=torch.float32)
+    rc = lib.fed_glm_family_batched(
+        X.data_ptr(), y.data_ptr(), offset.data_ptr() if offset is not None else None,
+        n, K, pieces.data_ptr(), _GLM_FAMILY_BATCHED_LINKS.index(link),
+        float(sigma), float(logp_const),
+        out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(),
+    )
+    _check(rc, "fed_glm_family_batched")
+    return out[:B], out[B:].reshape(K, B)

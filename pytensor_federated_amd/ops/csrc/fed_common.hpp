@@ -27,6 +27,8 @@
 //   glm_logistic_batched.hip  16-chain MFMA logistic kernels
 //   glm_family.hip            row-group single-chain kernel, link as a policy
 //                             (Poisson, Gaussian on K covariates, logistic)
+//   glm_family_batched.hip    16-chain MFMA kernel for the Poisson and Gaussian
+//                             links (the link policies are in glm_links.hpp)
 
 #pragma once
 

@@ -15,7 +15,7 @@
 // layout is exactly the wave-per-row kernel's.
 //
 // What turns z = x.beta (+ offset) into a logp term and a residual is the
-// link, a compile-time policy:
+// link, a compile-time policy (glm_links.hpp, shared with the batched kernel):
 //   Poisson  (log link)   term = y*z - exp(z)         resid = y - exp(z)
 //   Gaussian (identity)   term = -r*r/(2 sigma^2)     resid = r/sigma^2, r = y-z
 //   Logistic              the expressions of k_logistic_glm_reg, in its order
@@ -47,41 +47,7 @@
 // No inline assembly.  Measurements: profiles/PROFILES.md "GLM family kernel".
 
 #include "fed_common.hpp"
-
-enum FedLink { FED_LINK_POISSON = 0, FED_LINK_GAUSSIAN = 1, FED_LINK_LOGISTIC = 2 };
-
-struct LinkParams {
-    float inv_s2;       // 1 / sigma^2       (Gaussian)
-    float half_inv_s2;  // 1 / (2 sigma^2)   (Gaussian)
-};
-
-struct PoissonLink {
-    __device__ static __forceinline__ void eval(float y, float z, const LinkParams&,
-                                                float& term, float& resid) {
-        const float mu = __expf(z);  // z > 88: mu = inf, term = -inf (documented)
-        term = y * z - mu;
-        resid = y - mu;
-    }
-};
-
-struct GaussianLink {
-    __device__ static __forceinline__ void eval(float y, float z, const LinkParams& p,
-                                                float& term, float& resid) {
-        const float r = y - z;
-        term = -(r * r) * p.half_inv_s2;
-        resid = r * p.inv_s2;
-    }
-};
-
-struct LogisticLink {
-    __device__ static __forceinline__ void eval(float y, float z, const LinkParams&,
-                                                float& term, float& resid) {
-        // stable: y*z - softplus(z) = y*z - (max(z,0) + log1p(exp(-|z|)))
-        const float sp = fmaxf(z, 0.f) + log1pf(__expf(-fabsf(z)));
-        term = y * z - sp;
-        resid = y - 1.f / (1.f + __expf(-z));
-    }
-};
+#include "glm_links.hpp"
 
 // sum over the G lanes of a group; every lane of the group gets the total
 template <int G>
