@@ -31,6 +31,14 @@ Compute paths:
   (csrc/glm_family_batched.hip), one pass over X for all 16; theta and the
   residual travel as three bf16 pieces each, so nothing is rounded to bf16.
 
+Fisher information (``fisher_information``): ``H = X^T diag(w) X`` with
+``w = exp(z)`` (Poisson) or ``1/sigma^2`` (Gaussian).  Both links are
+canonical, so ``H`` is the expected and the observed information, the
+negative Hessian of ``logp``; it is a sum over rows, so shard matrices add.
+bf16 shards on the MI355X go through the MFMA kernel
+``ops.glm_family_fisher`` (csrc/glm_family_fisher.hip); everything else is
+a chunked eager ``X^T @ (w X)``.
+
 Overflow: the fp32 paths (the kernel, and eager on bf16/f32 data) form
 ``exp(z)`` in fp32.  For a row with ``z > 88`` that is ``inf``, so the
 Poisson ``logp`` is ``-inf`` and the gradient is not finite, in both paths
@@ -163,6 +171,10 @@ class _GLMFamilyModel(LogpGradModel):
     # -- what a family provides -------------------------------------------
     def _terms(self, y: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         """(per-row logp term, residual d term / d z), shaped like ``z``."""
+        raise NotImplementedError
+
+    def _weights(self, z: torch.Tensor) -> torch.Tensor:
+        """Fisher weight ``-d^2 term / dz^2`` per row, shaped like ``z``."""
         raise NotImplementedError
 
     _logp_const: float = 0.0
@@ -331,6 +343,113 @@ class _GLMFamilyModel(LogpGradModel):
             G += (Xf.t() @ resid).to(torch.float64)
         return logp, G
 
+    # -- Fisher information --------------------------------------------------
+    def fisher_information(self, beta, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``H(beta) = X^T diag(w(z)) X`` as fp64[K,K]: the negative Hessian
+        of ``logp`` (both links are canonical, so also the expected Fisher
+        information).  Zero-padded columns are sliced off.  ``out``
+        (fp64[K,K], same device) receives the result in place.
+
+        bf16 shards on the kernel path whose padded K is one of
+        ``ops.GLM_FAMILY_FISHER_K`` (up to 1024) go through the MFMA kernel
+        ``ops.glm_family_fisher``, where ``w*x`` is carried as three bf16
+        pieces so that no operand is rounded.  Everything else is eager
+        torch: CPU, ``use_kernels=False``, f32 and f64 shards, and a padded
+        K of 2048, which warns."""
+        beta = torch.as_tensor(beta)
+        if beta.shape != (self._k,):
+            raise ValueError(f"beta must have shape ({self._k},), got {tuple(beta.shape)}.")
+        if out is not None and (
+            out.dtype != torch.float64 or out.shape != (self._k, self._k)
+            or out.device != self._X.device
+        ):
+            raise ValueError(f"out must be fp64[{self._k}, {self._k}] on the shard's device")
+        if self._fisher_kernel_path():
+            from ..ops import glm_family_fisher
+
+            kw = dict(link=self._link, offset=self._offset, sigma=self._sigma)
+            beta = beta.to(device=self._X.device, dtype=torch.float32)
+            if self._k_pad:
+                beta = torch.cat(
+                    [beta, torch.zeros(self._k_pad, dtype=torch.float32, device=beta.device)]
+                )
+                H = glm_family_fisher(self._X, beta, **kw)[: self._k, : self._k]
+            elif out is not None and out.is_contiguous():
+                return glm_family_fisher(self._X, beta, out=out, **kw)
+            else:
+                H = glm_family_fisher(self._X, beta, **kw)
+        else:
+            H = self._fisher_eager(beta)
+        if out is not None:
+            out.copy_(H)
+            return out
+        return H
+
+    def _fisher_kernel_path(self) -> bool:
+        if self._X.dtype != torch.bfloat16 or not self._kernel_path():
+            return False
+        from ..ops import glm_family_fisher_supports
+
+        if not glm_family_fisher_supports(self._X.dtype, self._k_eff):
+            import warnings
+
+            warnings.warn(
+                f"GLM Fisher kernel not compiled for K={self._k_eff}; "
+                f"using the eager path. Supported: bf16 up to K=1024.",
+                stacklevel=3,
+            )
+            return False
+        return True
+
+    #: rows of one f32 chain of the eager Fisher matmul on a GPU.  The
+    #: device's f32 GEMM adds a long reduction in one chain, and its error
+    #: grows with the length: over 5000 rows up to 133 units of 2^-24 *
+    #: H_scale, at 128 rows 3.3 (measured on the accuracy sets).  The chains
+    #: are added in fp64.
+    _FISHER_CHAIN_ROWS = 128
+
+    def _fisher_eager(self, beta: torch.Tensor) -> torch.Tensor:
+        X = self._X[:, : self._k]
+        acc = self._acc_dtype
+        K = self._k
+        beta = beta.to(device=X.device, dtype=acc)
+        H = torch.zeros((K, K), dtype=torch.float64, device=X.device)
+        # short f32 chains on a GPU (one batched matmul per step, at most
+        # 256 MB of chain results); fp64 data and the CPU's BLAS need none
+        R = self._FISHER_CHAIN_ROWS if (X.is_cuda and acc != torch.float64) else 0
+        # chunked like _logp_grad_batched_eager: the upcast of X stays O(chunk)
+        chunked = X.dtype != acc and X.is_cuda and self._n > 1 << 20
+        step = 1 << 21 if chunked else max(self._n, 1)
+        if R:
+            step = min(step, R * max(1, (1 << 26) // (K * K)))
+        for s in range(0, self._n, step):
+            Xf = X[s : s + step].to(acc)
+            z = Xf @ beta
+            if self._offset is not None:
+                z = z + self._offset[s : s + step]
+            WX = self._weights(z)[:, None] * Xf
+            full = (Xf.shape[0] // R) * R if R else 0
+            if full:
+                H += torch.bmm(
+                    Xf[:full].reshape(-1, R, K).transpose(1, 2), WX[:full].reshape(-1, R, K)
+                ).sum(dim=0, dtype=torch.float64)
+            if full < Xf.shape[0]:
+                H += (Xf[full:].t() @ WX[full:]).to(torch.float64)
+        # X^T (w X) is symmetric only up to the matmul's rounding
+        return 0.5 * (H + H.t())
+
+    def as_fisher_func(self):
+        """A ``ComputeFunc``: numpy ``beta`` -> ``[H]`` (fp64[K,K]), which a
+        worker serves through ``ArraysToArraysService`` like any other."""
+
+        def fisher_func(beta):
+            # copy: wire-decoded arrays are read-only zero-copy views
+            b = torch.from_numpy(np.array(beta, dtype=np.float64))
+            H = self.fisher_information(b)
+            return [np.asarray(H.detach().cpu().double().numpy())]
+
+        return fisher_func
+
 
 class PoissonGLMModel(_GLMFamilyModel):
     """Federated worker model: Poisson regression (log link) on a private
@@ -377,6 +496,9 @@ class PoissonGLMModel(_GLMFamilyModel):
         mu = torch.exp(z)
         return y * z - mu, y - mu
 
+    def _weights(self, z):
+        return torch.exp(z)
+
 
 class GaussianGLMModel(_GLMFamilyModel):
     """Federated worker model: Gaussian regression on K covariates
@@ -410,3 +532,6 @@ class GaussianGLMModel(_GLMFamilyModel):
         r = y - z
         sig2 = self._sigma * self._sigma
         return -(r * r) * (0.5 / sig2), r * (1.0 / sig2)
+
+    def _weights(self, z):
+        return torch.full_like(z, 1.0 / (self._sigma * self._sigma))

@@ -30,6 +30,10 @@ __all__ = [
     "GLM_FAMILY_BATCHED_K",
     "glm_family_batched_supports",
     "glm_family_logp_grad_batched",
+    "GLM_FAMILY_FISHER_K",
+    "glm_family_fisher_supports",
+    "glm_family_fisher_tile_rows",
+    "glm_family_fisher",
     "ode_poly_logp_grad",
 ]
 
@@ -114,6 +118,15 @@ def _try_load() -> Optional[ctypes.CDLL]:
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
         ctypes.c_void_p,
     ]
+    lib.fed_glm_family_fisher.restype = ctypes.c_int
+    lib.fed_glm_family_fisher.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+        ctypes.c_void_p,
+    ]
+    lib.fed_glm_family_fisher_tile_rows.restype = ctypes.c_int
+    lib.fed_glm_family_fisher_tile_rows.argtypes = [ctypes.c_int]
     lib.fed_ode_lv_eval.restype = ctypes.c_int
     lib.fed_ode_lv_eval.argtypes = [
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -806,3 +819,90 @@ def glm_family_logp_grad_batched(
     )
     _check(rc, "fed_glm_family_batched")
     return out[:B], out[B:].reshape(K, B)
+
+
+#: feature counts the Fisher kernel is compiled for (the batched kernel's)
+GLM_FAMILY_FISHER_K = (8, 16, 32, 64, 128, 256, 512, 1024)
+#: fp32 slab of the Fisher kernel: at most 512 resident blocks (256 CUs x 2)
+#: of one 128 x 128 f32 panel pair each = 32 MiB (K < 128: 1024 blocks x 4
+#: slab rows of K*K floats at most, under 4 MiB).  For K > 128 the workspace
+#: also holds one f32 weight per row ahead of the slab.
+_GLM_FAMILY_FISHER_SLAB = (512 * 128 * 128 * 4) // 4
+
+
+def glm_family_fisher_supports(dtype, K: int) -> bool:
+    """True for bf16 shards with K in :data:`GLM_FAMILY_FISHER_K`."""
+    return dtype == torch.bfloat16 and int(K) in GLM_FAMILY_FISHER_K
+
+
+def glm_family_fisher_tile_rows(K: int) -> int:
+    """Rows per tile of the Fisher kernel at ``K`` (its edge-shape tests
+    take their row counts from it)."""
+    return int(require_kernels().fed_glm_family_fisher_tile_rows(int(K)))
+
+
+def glm_family_fisher(
+    X: torch.Tensor,
+    beta: torch.Tensor,
+    *,
+    link: str,
+    offset: Optional[torch.Tensor] = None,
+    sigma: float = 1.0,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Fisher information ``H = X^T diag(w) X`` of a Poisson or Gaussian GLM
+    on the matrix cores (csrc/glm_family_fisher.hip), as fp64[K,K].
+
+    ``w = exp(z)`` (Poisson) or ``1/sigma^2`` (Gaussian) with ``z = X @ beta
+    (+ offset)``; both links are canonical, so ``H`` is the negative Hessian
+    of logp.  ``X[N,K]`` is bf16 with K in :data:`GLM_FAMILY_FISHER_K`,
+    ``offset`` f32[N], ``beta`` any float [K] (used in f32, never rounded to
+    bf16).  ``w*x`` is split into three bf16 pieces on the device, so no
+    operand of the MFMA is rounded.  The result is exactly symmetric.
+    """
+    if link not in _GLM_FAMILY_BATCHED_LINKS:
+        raise ValueError(
+            f"unknown link {link!r}; expected one of {sorted(_GLM_FAMILY_BATCHED_LINKS)}"
+        )
+    if X.dim() != 2:
+        raise ValueError("X must be [N, K]")
+    n, K = X.shape
+    if X.dtype != torch.bfloat16:
+        raise TypeError(f"unsupported dtype {X.dtype}: the Fisher kernel reads bf16 X")
+    if not glm_family_fisher_supports(X.dtype, K):
+        raise ValueError(f"Fisher kernel not compiled for (dtype={X.dtype}, K={K})")
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+    if tuple(beta.shape) != (K,):
+        raise ValueError(f"beta must have shape ({K},), got {tuple(beta.shape)}")
+    if offset is not None and (
+        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
+    ):
+        raise ValueError("offset must be f32[N] on X's device")
+    _require_contiguous(X=X)
+    if offset is not None:
+        _require_contiguous(offset=offset)
+    if not X.is_cuda:
+        raise ValueError("X must be on a ROCm device")
+    if X.data_ptr() % 16:
+        raise ValueError("X must be 16-byte aligned")
+    if out is not None and (
+        out.dtype != torch.float64 or out.shape != (K, K) or out.device != X.device
+        or not out.is_contiguous()
+    ):
+        raise ValueError(f"out must be a contiguous fp64[{K}, {K}] on X's device")
+    lib = require_kernels()
+    beta_f32 = beta.detach().to(device=X.device, dtype=torch.float32).contiguous()
+    if out is None:
+        out = torch.empty((K, K), dtype=torch.float64, device=X.device)
+    w_elems = 4 * ((n + 3) // 4) if K > 128 else 0
+    ws = _workspace(
+        X.device, "glm_family_fisher", _GLM_FAMILY_FISHER_SLAB + w_elems, dtype=torch.float32
+    )
+    rc = lib.fed_glm_family_fisher(
+        X.data_ptr(), offset.data_ptr() if offset is not None else None,
+        n, K, beta_f32.data_ptr(), _GLM_FAMILY_BATCHED_LINKS.index(link), float(sigma),
+        out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(),
+    )
+    _check(rc, "fed_glm_family_fisher")
+    return out

@@ -29,6 +29,8 @@
 //                             (Poisson, Gaussian on K covariates, logistic)
 //   glm_family_batched.hip    16-chain MFMA kernel for the Poisson and Gaussian
 //                             links (the link policies are in glm_links.hpp)
+//   glm_family_fisher.hip     Fisher information X^T diag(w) X of the Poisson and
+//                             Gaussian links on the matrix cores
 
 #pragma once
 

@@ -1,6 +1,7 @@
 // Link policies of the GLM family kernels: what turns the linear predictor
 // z = x.beta (+ offset) of one row into its logp term and its residual
-// d term / d z.  Shared by the single-chain kernel (glm_family.hip) and the
+// d term / d z (eval), and into its Fisher weight -d^2 term / dz^2 (weight,
+// Poisson and Gaussian; used by glm_family_fisher.hip).  Shared by the single-chain kernel (glm_family.hip) and the
 // 16-chain MFMA kernel (glm_family_batched.hip), so both evaluate a row by
 // the same expressions in the same order.
 //   Poisson  (log link)   term = y*z - exp(z)         resid = y - exp(z)
@@ -32,6 +33,10 @@ struct PoissonLink {
         term = y * z - mu;
         resid = y - mu;
     }
+    // w = -d^2 term / dz^2 (the Fisher kernel's row weight)
+    __device__ static __forceinline__ void weight(float z, const LinkParams&, float& w) {
+        w = __expf(z);
+    }
 };
 
 struct GaussianLink {
@@ -40,6 +45,9 @@ struct GaussianLink {
         const float r = y - z;
         term = -(r * r) * p.half_inv_s2;
         resid = r * p.inv_s2;
+    }
+    __device__ static __forceinline__ void weight(float, const LinkParams& p, float& w) {
+        w = p.inv_s2;
     }
 };
 
