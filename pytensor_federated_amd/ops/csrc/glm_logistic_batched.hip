@@ -1,10 +1,24 @@
 // Batched (16-chain) logistic GLM on CDNA4 (gfx950) matrix cores: the MFMA
-// fragment-map probe, the five kernel variants (v1, v2, v3s, v3, whole-tile
-// LDS) and their dispatcher.  Every variant is kept: each is covered by the
-// exact-probe tests and serves as an A/B baseline.  Shared pieces and the
-// overview of the GLM units are in fed_common.hpp.
+// fragment-map probe, the kernels that ship (v3 at K=1024, v2 at K=512, v3s
+// as an opt-in), two A/B baselines (v1, whole-tile LDS) and their
+// dispatcher.  Every kernel here is covered by the exact-probe tests.
+// Shared pieces and the overview of the GLM units are in fed_common.hpp.
+//
+// History (ms at 2e6 x 1024 x 16 bf16, profiles/PROFILES.md): v1, a
+// double-buffered chunk pipeline that re-reads X for phase B, 1.568; v2,
+// v1 plus an XOR bank swizzle and a reverse phase-B chunk walk, 1.035 (the
+// 2x-traffic floor; 0.567 at K=512, where it is the default); v3, a
+// tile-resident LDS-DMA pipeline that reads X once, 0.878 (~0.95 same-box
+// against its successor); v3 on the transpose-read image, 0.89, the K=1024
+// default.  The LDS-resident whole-tile variant lost its round-1 A/B to v1
+// (no figure recorded).  The scalar-gather image of v3, its instrumented
+// build and the two environment flags that selected them last exist at
+// commit 5e9376b.
 
 #include "fed_common.hpp"
+
+typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
+typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 
 // ---------------------------------------------------------------------------
 // MFMA fragment-map probe (test-only): D = A[16x32] . B[32x16], bf16->f32.
@@ -14,16 +28,13 @@
 //   D: col   = lane&15, row = (lane>>4)*4 + reg
 // ---------------------------------------------------------------------------
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-
 __global__ __launch_bounds__(64) void k_mfma_probe(
     const unsigned short* __restrict__ A,  // [16][32] bf16 row-major
     const unsigned short* __restrict__ B,  // [32][16] bf16 row-major
     float* __restrict__ D                  // [16][16] f32 row-major
 ) {
     const int lane = threadIdx.x & 63;
-    union { bf16x8 v; unsigned short u[8]; } a_frag, b_frag;
+    union { bf16x8_t v; unsigned short u[8]; } a_frag, b_frag;
     const int arow = lane & 15;
     const int k0 = (lane >> 4) * 8;
 #pragma unroll
@@ -31,7 +42,7 @@ __global__ __launch_bounds__(64) void k_mfma_probe(
         a_frag.u[j] = A[arow * 32 + k0 + j];
         b_frag.u[j] = B[(k0 + j) * 16 + (lane & 15)];
     }
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
     acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_frag.v, b_frag.v, acc, 0, 0, 0);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -59,16 +70,19 @@ extern "C" int fed_mfma_probe(const void* A, const void* B, void* D, void* strea
 //     R[rows,16]  = y - sigmoid(Z)
 //     G[K,16]    += X^T[K,rows] . R[rows,16]       (phase B, MFMA)
 //
-// X is HBM-read once per call (k-chunks staged to LDS, phase B re-reads the
-// L2-hot chunk); at B=16 the arithmetic is 4*N*K*B flops -- VALU could not
-// keep up with the HBM stream (0.8 TFLOP/call vs ~4 ms of traffic), MFMA
-// makes compute a ~10% bystander.  Per-chain cost is ~B x lower than the
-// single-chain kernel.
+// X is HBM-read once per call (v1/v2: k-chunks staged to LDS, phase B
+// re-reads the L2-hot chunk; v3/v3s: the tile stays in LDS throughout); at
+// B=16 the arithmetic is 4*N*K*B flops -- VALU could not keep up with the
+// HBM stream (0.8 TFLOP/call vs ~4 ms of traffic), MFMA makes compute a
+// ~10% bystander.  Per-chain cost is ~B x lower than the single-chain
+// kernel.
 //
-// Geometry: block = 256 threads = 4 waves; row tile 64 (16 rows/wave in
-// phase A); K chunked by 128 (each wave owns a 32-col slice in phase B);
-// G accumulates in AGPRs (16 tiles x 4 f32/lane/wave); per-block partials
-// go to an fp32 slab [16 logp | K*16 G], reduced by k_colsum_reduce.
+// Geometry: block = 256 threads = 4 waves.  v1/v2: row tile 64 (16 rows/wave
+// in phase A); K chunked by 128 (each wave owns a 32-col slice in phase B).
+// v3/v3s: row tile 32, every wave owns a K slice in both phases.  G
+// accumulates in AGPRs (16 tiles x 4 f32/lane/wave at K=1024); per-block
+// partials go to an fp32 slab [16 logp | K*16 G], reduced by
+// k_colsum_reduce.
 //
 // Verified fragment maps (fed_mfma_probe): A[i=l&15][k=(l>>4)*8+j],
 // B[k=(l>>4)*8+j][j=l&15], D[col=l&15][row=(l>>4)*4+r].
@@ -80,8 +94,6 @@ extern "C" int fed_mfma_probe(const void* A, const void* B, void* D, void* strea
 #define TPAD 8           // Theta row pad: stride 2064+16 B
 #define RPAD 8           // R_T row pad: stride 144 B
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
 union frag_u { bf16x8_t v; unsigned short u[8]; U4 q; };
 
 // ---- pieces every batched kernel shares (all inlined; the kernels differ
@@ -472,19 +484,20 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v2(
 }
 
 // ---------------------------------------------------------------------------
-// Batched logistic v3: glds-staged, tile-RESIDENT -- phase B never re-reads
+// Batched logistic v3 / v3s: glds-staged, tile-RESIDENT, no phase-B re-read
 // ---------------------------------------------------------------------------
 // v2 sits at the 2x-traffic floor (~1.03 ms at 2e6x1024: phase B re-reads X
 // from HBM).  v3 removes the re-read: a 32-row x K tile stays resident in
-// LDS across BOTH phases.  Staging is global_load_lds (one 1-KB DMA per
-// 512-col row half, no VGPR round trip), pipelined one tile ahead through
-// three 32-KB half-buffers with COUNTED vmcnt waits and raw s_barriers (a
-// __syncthreads with a glds in flight drains the whole queue -- guide
-// "Pipelining across barriers").  1 block/CU, contiguous tile ranges.
+// LDS across BOTH phases.  Staging is global_load_lds (1-KB DMAs, no VGPR
+// round trip), pipelined one tile ahead through three 32-KB half-buffers
+// with COUNTED vmcnt waits and raw s_barriers (a __syncthreads with a glds
+// in flight drains the whole queue).  1 block/CU, contiguous tile ranges.
 // The counts (8 DMAs per wave per staged half) hold for full tiles only;
 // the problem's tail tile is processed outside the counted pipeline.
 //
-// Bank swizzle: the pad-free glds image (row stride 512 u16 == 0 mod 64
+// Two LDS images.  v3 (K=1024) stores [4][16] subtiles for the hardware
+// transpose read (v4_img below).  v3s (K=512) stores swizzled rows, one
+// 1-KB DMA per row: the pad-free image (row stride 512 u16 == 0 mod 64
 // dwords) would put every row on the same banks, so the SOURCE column
 // group of each lane is XOR-permuted by key(row) = rotl4_by2(row & 15):
 // 4-bit-injective (phase-A b128 slots stay distinct) and key(r) ^
@@ -511,9 +524,7 @@ __device__ __forceinline__ int v3_key(int row) {
         __builtin_amdgcn_s_barrier();                                   \
     } while (0)
 
-// stage rows [8w, 8w+8) of one 512-col half: one 1-KB LDS-DMA per row,
-// source columns pre-swizzled per lane.  dst rows are wave-uniform.
-//
+// One 1-KB LDS-DMA; the LDS destination is wave-uniform (m0).
 // The DMA is issued by INLINE ASM, not the builtin: hipcc tracks builtin
 // glds in its memory model and bundles `s_waitcnt vmcnt(0)` into the
 // lgkm wait of EVERY later ds_read that might alias -- which drains the
@@ -557,6 +568,8 @@ __device__ __forceinline__ unsigned v3_load_y_asm(const unsigned short* addr) {
     return v;
 }
 
+// Swizzled-row image (v3s): stage rows [8w, 8w+8) of one 512-col half, one
+// 1-KB LDS-DMA per row, source columns pre-swizzled per lane.
 __device__ __forceinline__ void v3_stage_half(
     const unsigned short* __restrict__ X, long long n_rows, int K,
     long long row0, int colbase, unsigned short* half_buf,
@@ -582,9 +595,10 @@ __device__ __forceinline__ void v3_stage_half(
     }
 }
 
-// v4 staging: one 1-KB DMA = 4 rows x 128 cols landing as 8 contiguous
-// [4][16] subtiles; per wave 8 DMAs (row-groups 2w..2w+1 x 4 col-octets),
-// so the v3 vmcnt ledgers hold unchanged on full tiles.  On the tail tile
+// Transpose-read image (v3): one 1-KB DMA = 4 rows x 128 cols landing as 8
+// contiguous [4][16] subtiles; per wave 8 DMAs (row-groups 2w..2w+1 x 4
+// col-octets), the same count as v3_stage_half, so one set of vmcnt
+// ledgers serves both images on full tiles.  On the tail tile
 // a wave issues 4 DMAs per fully valid row-group and none for an edge one
 // (v3_stage_half: one per valid row), so the kernel keeps the tail tile
 // out of the counted pipeline.  Lane n supplies the source of
@@ -799,9 +813,9 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3s(
     }
 }
 
-// v4 (TRB=1) image: X stored as row-major [4][16] subtiles so phase-B
+// v3's LDS image: X stored as row-major [4][16] subtiles so phase-B
 // fragments come from gfx950's hardware transpose-read (probe-verified
-// semantics, scripts/tr_probe.hip + gpurun_out/tr_probe.txt: each 16-lane
+// semantics, scripts/tr_probe.hip: each 16-lane
 // group hands lane (l&15) COLUMN l&15 of the 64-elem tile its addresses
 // cover, elems {base + (l&15) + 16j}).  Element offset of (row, col)
 // within a 32-row x 512-col half:
@@ -809,47 +823,24 @@ __device__ __forceinline__ int v4_img(int row, int col) {
     return (((row >> 2) * 32 + (col >> 4)) << 6) + ((row & 3) << 4) + (col & 15);
 }
 
-// Stage one half in either image (TRB=0: swizzled rows, TRB=1: [4][16]
-// subtiles).  The two phase-A and the two phase-B bodies of the kernel
-// below are NOT factored the same way: as helpers taking the half buffer
-// and the g_acc offset (or as one body in an unrolled two-step loop) they
-// compile to different address arithmetic, wait counts and register
-// counts, and this kernel is only changed when the result can be shown
-// unchanged.  A fix to one phase body goes into its twin as well.
-template <int TRB>
-__device__ __forceinline__ void stage_half(
-    const unsigned short* __restrict__ X, long long n_rows, int K,
-    long long row0, int colbase, unsigned short* half_buf,
-    const char* smem_base, int wid, int lane, int nt_on
-) {
-    if constexpr (TRB)
-        v4_stage_half(X, n_rows, K, row0, colbase, half_buf, smem_base, wid, lane, nt_on);
-    else
-        v3_stage_half(X, n_rows, K, row0, colbase, half_buf, smem_base, wid, lane, nt_on);
-}
-
-template <int PROF, int TRB>
+// The kernel below has two phase-A bodies (h0, h1) and two phase-B bodies
+// (h1, h0), all on the one [4][16]-subtile image.  They are NOT factored:
+// as helpers taking the half buffer and the g_acc offset (or as one body
+// in an unrolled two-step loop) they compile to different address
+// arithmetic, wait counts and register counts, and this kernel is only
+// changed when the result can be shown unchanged.  A fix to the body for
+// one half goes into the body for the other half as well.
 __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
     const unsigned short* __restrict__ X,   // [N][1024] bf16
     const unsigned short* __restrict__ y,   // [N] bf16
     long long n_rows,
     const unsigned short* __restrict__ theta_t,  // [16][1024] bf16
     float* __restrict__ slab,                    // [grid][16 + 1024*16]
-    int nt_on                                    // bit0: nt DMAs; bit1: profile
+    int nt_on                                    // bit0: nt on the tile DMAs (A/B)
 ) {
     constexpr int K = 2 * V3_HALF;
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
-    // FED_V3_PROF: wid-0 lane-0 of every block accumulates cycle counts
-    // for the two stage-gate waits, the mid (zc/R) barrier region and the
-    // phase-B h1 barrier into slab rows past the v3 grid (256 blocks x 8
-    // u64 in otherwise-unused workspace) -- splits PMC's "35% wait" into
-    // stage-starvation vs barrier-skew without touching the default path.
-    constexpr int prof_on = PROF;  // compile-time: the default instantiation
-                                   // carries ZERO instrumentation branches
-    unsigned long long p_gate1 = 0, p_gate4 = 0, p_mid = 0, p_bh = 0, p_t0 = 0;
-    unsigned long long p_phA = 0, p_phB = 0;
-    if (prof_on && wid == 0 && lane == 0) p_t0 = __builtin_amdgcn_s_memtime();
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     unsigned short* th_lds = (unsigned short*)smem;        // [16][K+TPAD]
@@ -886,14 +877,13 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
 
     // The counted vmcnt waits of the tile loop assume 8 DMAs per wave per
     // staged half.  The problem's TAIL tile (fewer than V3_ROWS valid rows)
-    // breaks that: a wave issues one DMA per valid row (v3 image) or 4 per
-    // fully valid row-group (v4 image) and fills the rest with LDS stores,
-    // so it owns anywhere from 0 to 8 -- a vmcnt(8) counted against such a
-    // half waits for too little and phase A may read rows that have not
-    // landed.  The tail tile therefore never enters the counted pipeline:
-    // pass 0 runs this block's FULL tiles with the exact ledger, pass 1
-    // runs the tail tile (owned by one block) on its own, fully drained
-    // before its first gate.  Both ranges are block-uniform.
+    // breaks that: a wave issues 4 DMAs per fully valid row-group and fills
+    // an edge row-group with LDS stores, so it owns 0, 4 or 8 -- a vmcnt(8)
+    // counted against such a half waits for too little and phase A may read
+    // rows that have not landed.  The tail tile therefore never enters the
+    // counted pipeline: pass 0 runs this block's FULL tiles with the exact
+    // ledger, pass 1 runs the tail tile (owned by one block) on its own,
+    // fully drained before its first gate.  Both ranges are block-uniform.
     const long long n_full = n_rows / V3_ROWS;  // tiles with every row valid
 #pragma unroll 1
     for (int pass = 0; pass < 2; ++pass) {
@@ -905,9 +895,9 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
         if (pass) V3_BARRIER();
         // prologue: stage tile p_begin fully.  h0 buffers alternate 0/2,
         // h1 lives in buffer 1.
-        stage_half<TRB>(X, n_rows, K, p_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
-        stage_half<TRB>(X, n_rows, K, p_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane,
-                        nt_on);
+        v4_stage_half(X, n_rows, K, p_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
+        v4_stage_half(X, n_rows, K, p_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane,
+                      nt_on);
         // the tail tile's short halves cannot be counted: drain them here,
         // which makes its gate [1] trivially true
         if (pass) V3_ASM_VMCNT(0);
@@ -922,12 +912,8 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
             const bool more = tile + 1 < p_end;
 
             // [1] own h0 DMAs done (h1's 8 may stay in flight), all waves
-            unsigned long long pt = 0;
-            if (prof_on && wid == 0 && lane == 0) pt = __builtin_amdgcn_s_memtime();
             V3_ASM_VMCNT(8);
             V3_BARRIER();
-            if (prof_on && wid == 0 && lane == 0)
-                p_gate1 += __builtin_amdgcn_s_memtime() - pt;
             // this thread's two y values (R-step slots), hidden loads on
             // the same queue, issued BEFORE the h0 prefetch so the [4]
             // counted wait (which leaves only the prefetch outstanding)
@@ -939,11 +925,9 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
             const unsigned yb1 = v3_load_y_asm(y + (yr1 > ymax ? ymax : yr1));
             // [2] prefetch next tile's h0 as deep as possible
             if (more)
-                stage_half<TRB>(X, n_rows, K, row0 + V3_ROWS, 0, h0n, smem, wid, lane, nt_on);
+                v4_stage_half(X, n_rows, K, row0 + V3_ROWS, 0, h0n, smem, wid, lane, nt_on);
 
             // ---- phase A on h0: z += X[:, w*128 .. +128) . theta ----
-            unsigned long long pa = 0;
-            if (prof_on && wid == 0 && lane == 0) pa = __builtin_amdgcn_s_memtime();
             f32x4_t z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
@@ -952,33 +936,22 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                 const int g = (kc >> 3) + (lane >> 4);  // 16B group in half
                 const int arow0 = lane & 15;            // rows 0..15
                 const int arow1 = 16 + (lane & 15);     // rows 16..31
-                if constexpr (TRB) {
-                    a0.q = *(U4*)&h0[v4_img(arow0, g * 8)];
-                    a1.q = *(U4*)&h0[v4_img(arow1, g * 8)];
-                } else {
-                    a0.q = *(U4*)&h0[arow0 * V3_HALF + ((g ^ v3_key(arow0)) * 8)];
-                    a1.q = *(U4*)&h0[arow1 * V3_HALF + ((g ^ v3_key(arow1)) * 8)];
-                }
+                a0.q = *(U4*)&h0[v4_img(arow0, g * 8)];
+                a1.q = *(U4*)&h0[v4_img(arow1, g * 8)];
                 const int bk = kc + (lane >> 4) * 8;    // theta col (h0)
                 b0f.q = *(U4*)&th_lds[(lane & 15) * th_stride + bk];
                 z0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0.v, b0f.v, z0, 0, 0, 0);
                 b1f.q = b0f.q;
                 z1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1.v, b1f.v, z1, 0, 0, 0);
             }
-            if (prof_on && wid == 0 && lane == 0)
-                p_phA += __builtin_amdgcn_s_memtime() - pa;
             // [4] own h1 DMAs + y loads done.  The count must match what
             // was actually issued after them: 8 prefetch DMAs on interior
             // tiles (the prefetched tile is always a full one -- the tail
             // tile is kept out of this pass), NOTHING on the last tile (an
             // unconditional vmcnt(8) there would leave h1/y unwaited -- a
             // timing-dependent race).
-            if (prof_on && wid == 0 && lane == 0) pt = __builtin_amdgcn_s_memtime();
             if (more) V3_ASM_VMCNT(8); else V3_ASM_VMCNT(0);
             V3_BARRIER();
-            if (prof_on && wid == 0 && lane == 0)
-                p_gate4 += __builtin_amdgcn_s_memtime() - pt;
-            if (prof_on && wid == 0 && lane == 0) pa = __builtin_amdgcn_s_memtime();
             // ---- phase A on h1 ----
 #pragma unroll
             for (int ks = 0; ks < 4; ++ks) {
@@ -987,20 +960,13 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                 const int g = (kc >> 3) + (lane >> 4);
                 const int arow0 = lane & 15;
                 const int arow1 = 16 + (lane & 15);
-                if constexpr (TRB) {
-                    a0.q = *(U4*)&h1[v4_img(arow0, g * 8)];
-                    a1.q = *(U4*)&h1[v4_img(arow1, g * 8)];
-                } else {
-                    a0.q = *(U4*)&h1[arow0 * V3_HALF + ((g ^ v3_key(arow0)) * 8)];
-                    a1.q = *(U4*)&h1[arow1 * V3_HALF + ((g ^ v3_key(arow1)) * 8)];
-                }
+                a0.q = *(U4*)&h1[v4_img(arow0, g * 8)];
+                a1.q = *(U4*)&h1[v4_img(arow1, g * 8)];
                 const int bk = V3_HALF + kc + (lane >> 4) * 8;  // theta col (h1)
                 bf.q = *(U4*)&th_lds[(lane & 15) * th_stride + bk];
                 z0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0.v, bf.v, z0, 0, 0, 0);
                 z1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1.v, bf.v, z1, 0, 0, 0);
             }
-            if (prof_on && wid == 0 && lane == 0)
-                p_phA += __builtin_amdgcn_s_memtime() - pa;
             // ---- combine the 4 waves' z quarters; logp + R ----
             {
                 float* zc = zc_lds + wid * V3_ROWS * BCH;
@@ -1010,10 +976,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                     zc[(16 + (lane >> 4) * 4 + r) * BCH + (lane & 15)] = z1[r];
                 }
             }
-            if (prof_on && wid == 0 && lane == 0) pt = __builtin_amdgcn_s_memtime();
             V3_BARRIER();
-            if (prof_on && wid == 0 && lane == 0)
-                p_mid += __builtin_amdgcn_s_memtime() - pt;
             {
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
@@ -1034,111 +997,64 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                     rt_lds[chain * rt_stride + row] = f32_to_bf16_rne_bits(resid);
                 }
             }
-            if (prof_on && wid == 0 && lane == 0) pt = __builtin_amdgcn_s_memtime();
             V3_BARRIER();  // R visible
-            if (prof_on && wid == 0 && lane == 0)
-                p_mid += __builtin_amdgcn_s_memtime() - pt;
 
-            if (prof_on && wid == 0 && lane == 0) pa = __builtin_amdgcn_s_memtime();
             // ---- phase B, h1 columns first (frees h1 for the refill) ----
 #pragma unroll
             for (int t2 = 0; t2 < 8; ++t2) {
                 const int kc = wid * 128 + t2 * 16;       // column in half
-                const int kcol = kc + (lane & 15);
                 f32x4_t acc = g_acc[8 + t2];
                 frag_u a, b;
-                if constexpr (TRB) {
-                    // two hardware transpose reads: lane (l&15) gets kcol
-                    // column kc+(l&15) for rows (l>>4)*8..+3 and +4..+7
-                    const unsigned base0 = (unsigned)((const char*)&h1[
-                        v4_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
-                    const unsigned base1 = (unsigned)((const char*)&h1[
-                        v4_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
-                    unsigned long long v0, v1;
-                    asm volatile(
-                        "ds_read_b64_tr_b16 %0, %2\n\t"
-                        "ds_read_b64_tr_b16 %1, %3\n\t"
-                        "s_waitcnt lgkmcnt(0)"
-                        : "=v"(v0), "=v"(v1) : "v"(base0), "v"(base1) : "memory");
-                    ((unsigned long long*)a.u)[0] = v0;
-                    ((unsigned long long*)a.u)[1] = v1;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int row = (lane >> 4) * 8 + j;
-                        a.u[j] = h1[row * V3_HALF +
-                                    (((kcol >> 3) ^ v3_key(row)) * 8) + (kcol & 7)];
-                    }
-                }
+                // two hardware transpose reads: lane (l&15) gets column
+                // kc+(l&15) for rows (l>>4)*8..+3 and +4..+7
+                const unsigned base0 = (unsigned)((const char*)&h1[
+                    v4_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
+                const unsigned base1 = (unsigned)((const char*)&h1[
+                    v4_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
+                unsigned long long v0, v1;
+                asm volatile(
+                    "ds_read_b64_tr_b16 %0, %2\n\t"
+                    "ds_read_b64_tr_b16 %1, %3\n\t"
+                    "s_waitcnt lgkmcnt(0)"
+                    : "=v"(v0), "=v"(v1) : "v"(base0), "v"(base1) : "memory");
+                ((unsigned long long*)a.u)[0] = v0;
+                ((unsigned long long*)a.u)[1] = v1;
                 b.q = *(U4*)&rt_lds[(lane & 15) * rt_stride + (lane >> 4) * 8];
                 g_acc[8 + t2] =
                     __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc, 0, 0, 0);
             }
-            if (prof_on && wid == 0 && lane == 0) {
-                p_phB += __builtin_amdgcn_s_memtime() - pa;
-                pt = __builtin_amdgcn_s_memtime();
-            }
             V3_BARRIER();  // everyone done reading h1
-            if (prof_on && wid == 0 && lane == 0)
-                p_bh += __builtin_amdgcn_s_memtime() - pt;
             // [6] refill h1 with the NEXT tile's second half
             if (more)
-                stage_half<TRB>(X, n_rows, K, row0 + V3_ROWS, V3_HALF, h1, smem, wid, lane, nt_on);
+                v4_stage_half(X, n_rows, K, row0 + V3_ROWS, V3_HALF, h1, smem, wid, lane, nt_on);
 
-            if (prof_on && wid == 0 && lane == 0) pa = __builtin_amdgcn_s_memtime();
             // ---- phase B, h0 columns ----
 #pragma unroll
             for (int t2 = 0; t2 < 8; ++t2) {
                 const int kc = wid * 128 + t2 * 16;
-                const int kcol = kc + (lane & 15);
                 f32x4_t acc = g_acc[t2];
                 frag_u a, b;
-                if constexpr (TRB) {
-                    // two hardware transpose reads: lane (l&15) gets kcol
-                    // column kc+(l&15) for rows (l>>4)*8..+3 and +4..+7
-                    const unsigned base0 = (unsigned)((const char*)&h0[
-                        v4_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
-                    const unsigned base1 = (unsigned)((const char*)&h0[
-                        v4_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
-                    unsigned long long v0, v1;
-                    asm volatile(
-                        "ds_read_b64_tr_b16 %0, %2\n\t"
-                        "ds_read_b64_tr_b16 %1, %3\n\t"
-                        "s_waitcnt lgkmcnt(0)"
-                        : "=v"(v0), "=v"(v1) : "v"(base0), "v"(base1) : "memory");
-                    ((unsigned long long*)a.u)[0] = v0;
-                    ((unsigned long long*)a.u)[1] = v1;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int row = (lane >> 4) * 8 + j;
-                        a.u[j] = h0[row * V3_HALF +
-                                    (((kcol >> 3) ^ v3_key(row)) * 8) + (kcol & 7)];
-                    }
-                }
+                // two hardware transpose reads, as for h1
+                const unsigned base0 = (unsigned)((const char*)&h0[
+                    v4_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
+                const unsigned base1 = (unsigned)((const char*)&h0[
+                    v4_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
+                unsigned long long v0, v1;
+                asm volatile(
+                    "ds_read_b64_tr_b16 %0, %2\n\t"
+                    "ds_read_b64_tr_b16 %1, %3\n\t"
+                    "s_waitcnt lgkmcnt(0)"
+                    : "=v"(v0), "=v"(v1) : "v"(base0), "v"(base1) : "memory");
+                ((unsigned long long*)a.u)[0] = v0;
+                ((unsigned long long*)a.u)[1] = v1;
                 b.q = *(U4*)&rt_lds[(lane & 15) * rt_stride + (lane >> 4) * 8];
                 g_acc[t2] =
                     __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc, 0, 0, 0);
             }
-            if (prof_on && wid == 0 && lane == 0)
-                p_phB += __builtin_amdgcn_s_memtime() - pa;
             h0sel ^= 2;
         }
     }
 
-    if (prof_on && wid == 0 && lane == 0) {
-        // rows >= 300 of the workspace slab are unused at v3's grid (256)
-        unsigned long long* prof =
-            (unsigned long long*)(slab + 300LL * (BCH + (long long)K * BCH)) +
-            8LL * blockIdx.x;
-        prof[0] = p_gate1;
-        prof[1] = p_gate4;
-        prof[2] = p_mid;
-        prof[3] = p_bh;
-        prof[4] = __builtin_amdgcn_s_memtime() - p_t0;
-        prof[5] = p_phA;
-        prof[6] = p_phB;
-    }
     // ---- epilogue: block partials -> slab (layout shared with v1/v2) ----
     // the two slots of one thread are chains (t&15) and ((t+256)&15) == same
     // chain, different rows -- so the plain per-chain strided sum works
@@ -1316,8 +1232,7 @@ extern "C" int fed_logistic_glm_batched(
     if (K != 512 && K != 1024) return -4;
 
     // Variant.  v3 (glds tile-resident, 1x HBM traffic) is the default at
-    // K=1024: 0.878 ms vs v2's 1.035 / v1's 1.568 at 2e6x1024x16, 5.17 ms
-    // at the config-4 shard (profiles/raw_r2/r2c10_*).  At K=512 the
+    // K=1024: 0.89 ms vs v2's 1.035 / v1's 1.568 at 2e6x1024x16.  At K=512 the
     // chunked v2 stays default: its 64-KB tiles already re-read through L2
     // (measured 0.567 ms ~= the 1x floor vs v3s 0.645 at 2e6x512 --
     // raw_r2/r2c12); FED_BATCHED_V3=1/0 forces either way.  The A/B
@@ -1367,19 +1282,9 @@ extern "C" int fed_logistic_glm_batched(
                        (const unsigned short*)theta_t_bf16, workspace, ##__VA_ARGS__)
 
     if (variant == V_V3) {
-        int nt_on = env_flag("FED_V3_NT", true);  // stream-once data: nt default
-        if (env_flag("FED_V3_PROF", false)) nt_on |= 2;
-        // tr_b16 phase-B image is the default: same-box A/B measured
-        // 0.888-0.891 vs 0.952-0.963 ms (3 reps, profiles raw_r2/v4_*);
-        // FED_BATCHED_V4=0 restores the scalar-gather image
-        if (K == 512)
-            LAUNCH_BATCHED(k_logistic_glm_batched_v3s<512>, nt_on);
-        else if (env_flag("FED_BATCHED_V4", true))
-            LAUNCH_BATCHED((k_logistic_glm_batched_v3<0, 1>), nt_on);
-        else if (nt_on & 2)
-            LAUNCH_BATCHED((k_logistic_glm_batched_v3<1, 0>), nt_on);
-        else
-            LAUNCH_BATCHED((k_logistic_glm_batched_v3<0, 0>), nt_on);
+        const int nt_on = env_flag("FED_V3_NT", true);  // stream-once data: nt default
+        if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched_v3, nt_on);
+        else LAUNCH_BATCHED(k_logistic_glm_batched_v3s<512>, nt_on);
     } else if (variant == V_V2) {
         if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched_v2<1024>);
         else LAUNCH_BATCHED(k_logistic_glm_batched_v2<512>);

@@ -18,14 +18,13 @@ pytestmark = pytest.mark.gpu
 from pytensor_federated_amd.models import GaussianLinearModel, LogisticGLMModel
 
 BATCHED_ENV = (
-    "FED_BATCHED_V1", "FED_BATCHED_V3", "FED_BATCHED_V4", "FED_BATCHED_LDS",
-    "FED_BATCHED_GRID", "FED_V3_NT", "FED_V3_PROF",
+    "FED_BATCHED_V1", "FED_BATCHED_V3", "FED_BATCHED_LDS",
+    "FED_BATCHED_GRID", "FED_V3_NT",
 )
 
 #: id -> (K, kernel-selection switches); read by getenv on every call
 BATCHED_VARIANTS = {
     "v3tr_k1024": (1024, {}),                         # default: v3, tr image
-    "v3scalar_k1024": (1024, {"FED_BATCHED_V4": "0"}),
     "v2_k1024": (1024, {"FED_BATCHED_V3": "0"}),
     "v2_k512": (512, {}),                             # default at K=512
     "v3s_k512": (512, {"FED_BATCHED_V3": "1"}),
