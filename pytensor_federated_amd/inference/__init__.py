@@ -13,5 +13,6 @@ from .mala import sample_mala_batched  # noqa: F401
 from .map import find_map  # noqa: F401
 from .mcmc import Metropolis, sample_metropolis  # noqa: F401
 from .newton import NewtonResult, find_map_newton, laplace_mass  # noqa: F401
+from .newton_cg import NewtonCGResult, find_map_newton_cg  # noqa: F401
 from .nuts import NUTS, sample_nuts  # noqa: F401
 from .nuts_batched import sample_nuts_batched  # noqa: F401

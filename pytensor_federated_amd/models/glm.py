@@ -39,6 +39,12 @@ bf16 shards on the MI355X go through the MFMA kernel
 ``ops.glm_family_fisher`` (csrc/glm_family_fisher.hip); everything else is
 a chunked eager ``X^T @ (w X)``.
 
+Fisher-vector product and diagonal (``fisher_vector_product``,
+``fisher_diagonal``; models/fisher_vector.py): ``H v`` and ``diag(H)`` in one
+pass over the shard each, a K-vector as the result.  On the MI355X they run
+on ``ops.glm_family_fisher_vector`` (csrc/glm_family_fvp.hip) wherever
+``logp_grad`` runs on its kernel, f32 shards and a padded K of 2048 included.
+
 Overflow: the fp32 paths (the kernel, and eager on bf16/f32 data) form
 ``exp(z)`` in fp32.  For a row with ``z > 88`` that is ``inf``, so the
 Poisson ``logp`` is ``-inf`` and the gradient is not finite, in both paths
@@ -54,6 +60,7 @@ import numpy as np
 import torch
 
 from .base import LogpGradModel
+from .fisher_vector import FisherVectorMixin
 
 __all__ = [
     "PoissonGLMModel",
@@ -109,7 +116,7 @@ def _as_tensor(a) -> torch.Tensor:
     return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
 
 
-class _GLMFamilyModel(LogpGradModel):
+class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
     """What the families share: the shard, zero-column padding to a kernel
     size, the kernel/eager dispatch and the ``out=`` seam.  A family names
     its ``_link`` and gives ``_terms`` (the eager per-row logp term and
@@ -449,6 +456,10 @@ class _GLMFamilyModel(LogpGradModel):
             return [np.asarray(H.detach().cpu().double().numpy())]
 
         return fisher_func
+
+    # -- Fisher-vector product (FisherVectorMixin) ----------------------------
+    def _fvp_kernel_path(self) -> bool:
+        return self._kernel_path()
 
 
 class PoissonGLMModel(_GLMFamilyModel):

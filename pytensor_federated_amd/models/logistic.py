@@ -16,6 +16,13 @@ Compute paths:
   tile is still in registers.  At N=1e8 x K=1024 bf16 the shard is 25.6 GB
   per GPU; the op is HBM-bound, so single-pass is ~2x over the eager
   two-matmul shape.
+
+Second order (``fisher_vector_product``, ``fisher_diagonal``;
+models/fisher_vector.py): ``H v = X^T (w * (X v))`` and ``diag(H)`` with
+``w = mu (1 - mu)``, one pass over the shard each.  The padded K of the fused
+kernel is also a size of the row-group family kernel, so on the MI355X the
+stored X goes to ``ops.glm_family_fisher_vector`` with ``link="logistic"`` as
+it is; other shapes, the CPU and ``use_kernels=False`` are eager.
 """
 from __future__ import annotations
 
@@ -25,6 +32,7 @@ import numpy as np
 import torch
 
 from .base import LogpGradModel
+from .fisher_vector import FisherVectorMixin
 
 __all__ = ["LogisticGLMModel", "generate_logistic_dataset"]
 
@@ -45,10 +53,15 @@ def generate_logistic_dataset(
     return X, y, beta
 
 
-class LogisticGLMModel(LogpGradModel):
+class LogisticGLMModel(FisherVectorMixin, LogpGradModel):
     """Federated worker model: logistic regression on a private shard."""
 
     param_names = ("beta",)
+    # what FisherVectorMixin reads: the link of ops.glm_family_fisher_vector,
+    # no offset, no noise scale
+    _link = "logistic"
+    _offset = None
+    _sigma = 1.0
 
     def __init__(
         self,
@@ -125,6 +138,25 @@ class LogisticGLMModel(LogpGradModel):
     def fused_size(self) -> int:
         """Layout of the fused fp64 output buffer: [logp, grad[K]]."""
         return 1 + int(self._k)
+
+    # -- Fisher-vector product (FisherVectorMixin) ----------------------------
+    @property
+    def _acc_dtype(self) -> torch.dtype:
+        return torch.float64 if self._X.dtype == torch.float64 else torch.float32
+
+    def _weights(self, z: torch.Tensor) -> torch.Tensor:
+        mu = torch.sigmoid(z)
+        return mu * (1.0 - mu)
+
+    def _fvp_kernel_path(self) -> bool:
+        """No warning: a shape without a kernel (a padded K of 1536) is
+        eager here as it is for ``logp_grad``, which says so."""
+        want = self._X.is_cuda if self._use_kernels is None else self._use_kernels
+        if not want:
+            return False
+        from ..ops import glm_family_kernel_supports
+
+        return glm_family_kernel_supports(self._X.dtype, self._k_eff)
 
     def logp_grad(
         self, beta, out: Optional[torch.Tensor] = None

@@ -34,6 +34,8 @@ __all__ = [
     "glm_family_fisher_supports",
     "glm_family_fisher_tile_rows",
     "glm_family_fisher",
+    "glm_family_fisher_vector",
+    "glm_family_fisher_diagonal",
     "ode_poly_logp_grad",
 ]
 
@@ -124,6 +126,13 @@ def _try_load() -> Optional[ctypes.CDLL]:
         ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
         ctypes.c_void_p,
+    ]
+    lib.fed_glm_family_fvp.restype = ctypes.c_int
+    lib.fed_glm_family_fvp.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_double,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+        ctypes.c_int, ctypes.c_void_p,
     ]
     lib.fed_glm_family_fisher_tile_rows.restype = ctypes.c_int
     lib.fed_glm_family_fisher_tile_rows.argtypes = [ctypes.c_int]
@@ -906,3 +915,102 @@ def glm_family_fisher(
     )
     _check(rc, "fed_glm_family_fisher")
     return out
+
+
+def _glm_family_fvp(
+    X: torch.Tensor,
+    beta: torch.Tensor,
+    v: Optional[torch.Tensor],
+    *,
+    link: str,
+    offset: Optional[torch.Tensor],
+    sigma: float,
+    out: Optional[torch.Tensor],
+) -> torch.Tensor:
+    """What the product and the diagonal share: ``v is None`` is the diagonal."""
+    if link not in GLM_FAMILY_LINKS:
+        raise ValueError(f"unknown link {link!r}; expected one of {sorted(GLM_FAMILY_LINKS)}")
+    if X.dim() != 2:
+        raise ValueError("X must be [N, K]")
+    n, K = X.shape
+    if X.dtype not in _GLM_FAMILY_VEC:
+        raise TypeError(f"unsupported dtype {X.dtype}")
+    if not glm_family_kernel_supports(X.dtype, K):
+        raise ValueError(f"family kernel not compiled for (dtype={X.dtype}, K={K})")
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+    if tuple(beta.shape) != (K,):
+        raise ValueError(f"beta must have shape ({K},), got {tuple(beta.shape)}")
+    if v is not None and tuple(v.shape) != (K,):
+        raise ValueError(f"v must have shape ({K},), got {tuple(v.shape)}")
+    if offset is not None and (
+        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
+    ):
+        raise ValueError("offset must be f32[N] on X's device")
+    _require_contiguous(X=X)
+    if offset is not None:
+        _require_contiguous(offset=offset)
+    if not X.is_cuda:
+        raise ValueError("X must be on a ROCm device")
+    if X.data_ptr() % 16:
+        raise ValueError("X must be 16-byte aligned")
+    if out is not None and (
+        out.dtype != torch.float64 or out.shape != (K,) or out.device != X.device
+        or not out.is_contiguous()
+    ):
+        raise ValueError(f"out must be a contiguous fp64[{K}] on X's device")
+    lib = require_kernels()
+    beta_f32 = beta.detach().to(device=X.device, dtype=torch.float32).contiguous()
+    v_f32 = None if v is None else v.detach().to(device=X.device, dtype=torch.float32).contiguous()
+    if out is None:
+        out = torch.empty(K, dtype=torch.float64, device=X.device)
+    # a slab of its own: glm_family_logp_grad's may be in use on another stream
+    ws = _workspace(X.device, f"glm_family_fvp{K}", 1024 * K, dtype=torch.float32)
+    rc = lib.fed_glm_family_fvp(
+        X.data_ptr(), offset.data_ptr() if offset is not None else None, n, K,
+        beta_f32.data_ptr(), v_f32.data_ptr() if v_f32 is not None else None,
+        GLM_FAMILY_LINKS[link], float(sigma),
+        out.data_ptr(), ws.data_ptr(), ws.numel() * 4,
+        _DTYPE_CODE[X.dtype], _stream_ptr(),
+    )
+    _check(rc, "fed_glm_family_fvp")
+    return out
+
+
+def glm_family_fisher_vector(
+    X: torch.Tensor,
+    beta: torch.Tensor,
+    v: torch.Tensor,
+    *,
+    link: str,
+    offset: Optional[torch.Tensor] = None,
+    sigma: float = 1.0,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Fisher-vector product ``H v = X^T (w * (X v))`` of a GLM in one pass
+    over X (csrc/glm_family_fvp.hip), as fp64[K]; no ``K x K`` object is formed.
+
+    ``w = exp(z)`` (``"poisson"``), ``1/sigma^2`` (``"gaussian"``) or
+    ``mu (1 - mu)``, ``mu = sigmoid(z)`` (``"logistic"``), with ``z = X @ beta
+    (+ offset)``.  ``X[N,K]`` is bf16 or f32 with K one of the sizes of
+    :func:`glm_family_padded_k`; ``offset`` is f32[N]; ``beta`` and ``v`` are
+    any float [K], used in f32.
+    """
+    if v is None:
+        raise ValueError("v must have shape (K,); see glm_family_fisher_diagonal")
+    return _glm_family_fvp(X, beta, v, link=link, offset=offset, sigma=sigma, out=out)
+
+
+def glm_family_fisher_diagonal(
+    X: torch.Tensor,
+    beta: torch.Tensor,
+    *,
+    link: str,
+    offset: Optional[torch.Tensor] = None,
+    sigma: float = 1.0,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """``diag(H)[k] = sum_r w_r x_rk^2`` as fp64[K], by the kernel of
+    :func:`glm_family_fisher_vector` and under the same conditions: the
+    Jacobi preconditioner of a conjugate-gradient solve with ``H``."""
+    return _glm_family_fvp(X, beta, None, link=link, offset=offset, sigma=sigma, out=out)

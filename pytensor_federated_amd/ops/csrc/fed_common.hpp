@@ -31,6 +31,9 @@
 //                             links (the link policies are in glm_links.hpp)
 //   glm_family_fisher.hip     Fisher information X^T diag(w) X of the Poisson and
 //                             Gaussian links on the matrix cores
+//   glm_family_fvp.hip        Fisher-vector product X^T (w * (X v)) and diag(H)
+//                             of all three links, one pass in the row-group
+//                             geometry
 
 #pragma once
 

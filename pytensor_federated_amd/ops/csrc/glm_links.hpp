@@ -1,7 +1,8 @@
 // Link policies of the GLM family kernels: what turns the linear predictor
 // z = x.beta (+ offset) of one row into its logp term and its residual
-// d term / d z (eval), and into its Fisher weight -d^2 term / dz^2 (weight,
-// Poisson and Gaussian; used by glm_family_fisher.hip).  Shared by the single-chain kernel (glm_family.hip) and the
+// d term / d z (eval), and into its Fisher weight -d^2 term / dz^2 (weight;
+// used by glm_family_fisher.hip, Poisson and Gaussian, and by
+// glm_family_fvp.hip, all three).  Shared by the single-chain kernel (glm_family.hip) and the
 // 16-chain MFMA kernel (glm_family_batched.hip), so both evaluate a row by
 // the same expressions in the same order.
 //   Poisson  (log link)   term = y*z - exp(z)         resid = y - exp(z)
@@ -58,5 +59,11 @@ struct LogisticLink {
         const float sp = fmaxf(z, 0.f) + log1pf(__expf(-fabsf(z)));
         term = y * z - sp;
         resid = y - 1.f / (1.f + __expf(-z));
+    }
+    // w = mu * (1 - mu), mu formed as eval forms it (glm_family_fvp.hip; the
+    // Fisher MFMA kernel has no logistic weight)
+    __device__ static __forceinline__ void weight(float z, const LinkParams&, float& w) {
+        const float mu = 1.f / (1.f + __expf(-z));
+        w = mu * (1.f - mu);
     }
 };
