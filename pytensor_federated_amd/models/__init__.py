@@ -8,4 +8,5 @@ from .glm import (  # noqa: F401
 )
 from .linear import GaussianLinearModel, generate_linear_dataset  # noqa: F401
 from .logistic import LogisticGLMModel, generate_logistic_dataset  # noqa: F401
+from .softmax import SoftmaxGLMModel, generate_softmax_dataset  # noqa: F401
 from .ode import ODEModel, generate_ode_dataset, lotka_volterra_rhs  # noqa: F401

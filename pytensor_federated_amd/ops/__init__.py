@@ -30,6 +30,10 @@ __all__ = [
     "GLM_FAMILY_BATCHED_K",
     "glm_family_batched_supports",
     "glm_family_logp_grad_batched",
+    "GLM_SOFTMAX_MAX_CLASSES",
+    "glm_softmax_supports",
+    "glm_softmax_class_group",
+    "glm_softmax_logp_grad",
     "GLM_FAMILY_FISHER_K",
     "glm_family_fisher_supports",
     "glm_family_fisher_tile_rows",
@@ -117,6 +121,13 @@ def _try_load() -> Optional[ctypes.CDLL]:
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
         ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
         ctypes.c_double, ctypes.c_double,
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+        ctypes.c_void_p,
+    ]
+    lib.fed_glm_softmax_batched.restype = ctypes.c_int
+    lib.fed_glm_softmax_batched.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+        ctypes.c_void_p, ctypes.c_int,
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
         ctypes.c_void_p,
     ]
@@ -828,6 +839,91 @@ def glm_family_logp_grad_batched(
     )
     _check(rc, "fed_glm_family_batched")
     return out[:B], out[B:].reshape(K, B)
+
+
+#: classes the softmax stage of the batched family kernel covers: its 16
+#: MFMA columns hold 16 // CP chains of CP class slots each
+GLM_SOFTMAX_MAX_CLASSES = BATCH_CHAINS
+
+
+def glm_softmax_class_group(n_classes: int) -> int:
+    """CP: the class-group width, the next power of two >= ``n_classes``
+    (2, 4, 8 or 16).  One launch carries ``16 // CP`` chains."""
+    n_classes = int(n_classes)
+    if not 2 <= n_classes <= GLM_SOFTMAX_MAX_CLASSES:
+        raise ValueError(
+            f"n_classes must be in [2, {GLM_SOFTMAX_MAX_CLASSES}], got {n_classes}"
+        )
+    cp = 2
+    while cp < n_classes:
+        cp *= 2
+    return cp
+
+
+def glm_softmax_supports(dtype, K: int, n_classes: int) -> bool:
+    """True for bf16 shards with K in :data:`GLM_FAMILY_BATCHED_K` and
+    2 <= ``n_classes`` <= 16."""
+    return (
+        glm_family_batched_supports(dtype, K)
+        and 2 <= int(n_classes) <= GLM_SOFTMAX_MAX_CLASSES
+    )
+
+
+def glm_softmax_logp_grad(
+    X: torch.Tensor,
+    y: torch.Tensor,
+    theta16: torch.Tensor,
+    *,
+    n_classes: int,
+    out: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``16 // CP`` chains of a softmax (multinomial) GLM in one pass over X,
+    on the matrix cores (csrc/glm_family_batched.hip with the row-coupled
+    softmax stage): ``(logp[16 // CP], G[K,16])``.
+
+    ``theta16[K,16]`` is the packed image: with ``CP =
+    glm_softmax_class_group(n_classes)``, column ``g*CP + c`` is class ``c``
+    of chain ``g``.  Columns of padded classes (``c >= n_classes``) are not
+    read into any result and their columns of ``G`` are exactly 0.
+    ``X[N,K]`` is bf16 with K in :data:`GLM_FAMILY_BATCHED_K`; ``y`` holds
+    the labels in ``[0, n_classes)`` as f32[N].  theta travels as the three
+    bf16 pieces of :func:`split_bf16x3` and the residual is split the same
+    way on the device, so no operand is rounded.  ``G`` is an fp64 view of
+    ``out`` (fp64[16 + K*16]); ``logp`` sums the per-column fp64 sums in
+    ``out[:16]`` over each class group.
+    """
+    lib = require_kernels()
+    n, K = X.shape
+    B = BATCH_CHAINS
+    if X.dtype != torch.bfloat16:
+        raise TypeError(f"unsupported dtype {X.dtype}: the softmax kernel reads bf16 X")
+    if not glm_family_batched_supports(X.dtype, K):
+        raise ValueError(f"softmax kernel not compiled for (dtype={X.dtype}, K={K})")
+    cp = glm_softmax_class_group(n_classes)
+    if not X.is_cuda:
+        raise ValueError("X must be on a ROCm device")
+    if y.dtype != torch.float32 or y.shape != (n,) or y.device != X.device:
+        raise ValueError("y must be f32[N] on X's device")
+    _require_contiguous(X=X, y=y)
+    if X.data_ptr() % 16:
+        raise ValueError("X must be 16-byte aligned")
+    if tuple(theta16.shape) != (K, B):
+        raise ValueError(f"theta16 must be [{K}, {B}], got {tuple(theta16.shape)}")
+    pieces = split_bf16x3(theta16.to(device=X.device))
+    if out is None:
+        out = torch.empty(B + K * B, dtype=torch.float64, device=X.device)
+    elif (
+        out.dtype != torch.float64 or out.shape != (B + K * B,) or out.device != X.device
+        or not out.is_contiguous()
+    ):
+        raise ValueError(f"out must be a contiguous fp64[{B + K * B}] on X's device")
+    ws = _workspace(X.device, "glm_softmax", _GLM_FAMILY_BATCHED_WS, dtype=torch.float32)
+    rc = lib.fed_glm_softmax_batched(
+        X.data_ptr(), y.data_ptr(), n, K, pieces.data_ptr(), int(n_classes),
+        out.data_ptr(), ws.data_ptr(), ws.numel() * 4, _stream_ptr(),
+    )
+    _check(rc, "fed_glm_softmax_batched")
+    return out[:B].reshape(B // cp, cp).sum(dim=1), out[B:].reshape(K, B)
 
 
 #: feature counts the Fisher kernel is compiled for (the batched kernel's)

@@ -1,11 +1,13 @@
-// Batched (16-chain) GLM families on CDNA4 (gfx950) matrix cores:
-// k_glm_family_batched and its C entry point fed_glm_family_batched, for the
-// Poisson and Gaussian links of glm_links.hpp.  Shared pieces and the
-// overview of the GLM units are in fed_common.hpp; the fragment maps are
-// the ones glm_logistic_batched.hip verifies with fed_mfma_probe.
+// Batched (16-column) GLM families on CDNA4 (gfx950) matrix cores:
+// k_glm_family_batched and its C entry points fed_glm_family_batched, for the
+// Poisson and Gaussian links of glm_links.hpp (16 chains), and
+// fed_glm_softmax_batched, for the softmax GLM (16/CP chains of CP class
+// slots).  Shared pieces and the overview of the GLM units are in
+// fed_common.hpp; the fragment maps are the ones glm_logistic_batched.hip
+// verifies with fed_mfma_probe.
 //
 //     Z[rows,16] = X[rows,K] . Theta[K,16] (+ offset[rows])   phase A, MFMA
-//     term, resid = Link::eval(y, z)                          per (row, chain), f32
+//     term, resid = Stage::eval(y, z, column)                 per (row, column), f32
 //     logp[b]   += term                                       fp64 from the thread outwards
 //     G[K,16]   += X^T[K,rows] . R[rows,16]                   phase B, MFMA
 //
@@ -19,6 +21,28 @@
 // one accumulator per piece, summed smallest piece first.  The residual is
 // split the same way in the kernel into RP pieces (template parameter,
 // default 3: exact) and phase B issues RP MFMAs per gathered X^T fragment.
+//
+// Middle stage (glm_links.hpp).  The kernel is a template over what a
+// thread does with the z of its (row, column) slot; staging, phase A, phase
+// B and the epilogue exist once.
+//   ElementStage<Link>  the 16 columns are 16 independent chains; a slot is
+//       evaluated on its own by Link::eval (Poisson, Gaussian).
+//   SoftmaxStage        the 16 columns are 16/CP chains of CP class slots,
+//       CP the next power of two >= C (2, 4, 8 or 16; a wave-uniform kernel
+//       argument, not a template parameter: 8 instantiations instead of 32);
+//       column g*CP + c is class c of chain g and y is the row's label.  A
+//       padded class (c >= C) takes z = -inf, so its e and residual are 0
+//       and its G column is exactly 0.  m = max and s = sum exp(z - m) over
+//       the group are DPP butterflies (quad_perm x2, row_half_mirror,
+//       row_mirror through __builtin_amdgcn_update_dpp; four steps, those
+//       at or past CP masked): slot = tid + s*256 puts the 16 columns of a
+//       row into the 16 adjacent lanes of one DPP row and every lane runs
+//       the same SPT trips of the slot loop, so the cross-lane steps are
+//       legal.
+//       The lane c == y adds (z - m) - log(s) to its fp64 logp; out[0..16)
+//       stay per-column sums and the host adds the CP columns of a chain.
+//       Rows past n_rows are zero-filled, so their z are finite before the
+//       mask (no NaN forms); |z| in the thousands stays finite.
 //
 // Geometry.  Block = 256 threads = 4 waves; a wave always works on 32 rows
 // (two 16-row phase-A fragments, one 32-row phase-B reduction).
@@ -37,7 +61,7 @@
 //
 // One tile: stage X (16-byte groups, four loads in flight per thread), y and
 // offset (f32) into LDS | barrier | phase A from LDS, partial Z to LDS |
-// barrier | one thread per (row, chain) slot: z, Link::eval, fp64 logp,
+// barrier | one thread per (row, chain) slot: z, Stage::eval, fp64 logp,
 // residual pieces to LDS (R^T image [piece][chain][row]) | barrier | phase
 // B: X^T fragments by the u16 LDS gather of the v1/v2 logistic kernels |
 // barrier.  X is read from HBM exactly once.
@@ -52,13 +76,14 @@
 // sums are added with atomicAdd(double) into out[chain]; block 0 adds
 // logp_const.
 //
-// Registers.  gfx950 ISA of all 16 instantiations (2 links x 8 K, RP = 3)
-// checked with
+// Registers.  gfx950 ISA of all 24 instantiations (2 links and the softmax
+// stage x 8 K, RP = 3) checked with
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -S --cuda-device-only \
 //         -Rpass-analysis=kernel-resource-usage glm_family_batched.hip
 // every one reports ScratchSize 0 and no VGPR/SGPR spill; the counts are in
-// the table at the dispatcher.  No inline assembly.
-// Measurements: profiles/PROFILES.md "GLM family batched kernel".
+// the tables at the dispatcher.  No inline assembly.
+// Measurements: profiles/PROFILES.md "GLM family batched kernel" and
+// "Softmax GLM".
 
 #include "fed_common.hpp"
 #include "glm_links.hpp"
@@ -101,14 +126,14 @@ struct FbGeom {
     static_assert(X_BYTES % 16 == 0 && (FB_CH * RS * 2) % 16 == 0, "16-byte LDS sections");
 };
 
-template <class Link, int K, int RP>
+template <class Stage, int K, int RP>
 __global__ __launch_bounds__(256) void k_glm_family_batched(
     const unsigned short* __restrict__ X,        // [N][K] bf16 row-major
     const float* __restrict__ y,                 // [N]
     const float* __restrict__ offset,            // [N] or NULL
     long long n_rows,
     const unsigned short* __restrict__ theta_p,  // [3][16][K] bf16 pieces, transposed
-    LinkParams lp,
+    typename Stage::Params lp,
     double logp_const,
     double* __restrict__ logp_out,               // [16], pre-zeroed
     float* __restrict__ slab                     // [gridDim * WR][K*16]
@@ -230,7 +255,7 @@ __global__ __launch_bounds__(256) void k_glm_family_batched(
             for (int w = 1; w < WK; ++w) zs += zc_lds[(w * TR + row) * FB_CH + chain];
             const float z = off_lds[row] + zs;
             float term, resid;
-            Link::eval(y_lds[row], z, lp, term, resid);
+            Stage::eval(y_lds[row], z, chain, lp, term, resid);
             if (row0 + row >= n_rows) {
                 term = 0.f;
                 resid = 0.f;
@@ -317,29 +342,89 @@ static int fb_blocks_per_cu(int K) {
     }
 }
 
-template <class Link, int K>
+// SoftmaxStage (8 more instantiations):
+//      K   VGPRs    AGPRs  occupancy
+//      8    117        8       4
+//     16     99        8       4
+//     32    106       12       4
+//     64    155       28       2
+//    128     77       16       5
+//    256    123       28       3
+//    512    141       52       2
+//   1024    222       88       1
+// All 8: ScratchSize 0, no SGPR or VGPR spill; LDS and occupancy as above,
+// so both entry points size the grid by fb_blocks_per_cu.  (With the
+// __shfl_xor butterfly the DPP one replaced, four more VGPRs each held the
+// lane addresses, and K = 8 and 32 passed 128 registers: occupancy 3.)
+
+template <class Stage, int K>
 static void launch_fb(int grid, hipStream_t stream, const void* X, const float* y,
-                      const float* offset, long long n_rows, const void* theta_p, LinkParams lp,
-                      double logp_const, double* out, float* workspace) {
+                      const float* offset, long long n_rows, const void* theta_p,
+                      typename Stage::Params lp, double logp_const, double* out,
+                      float* workspace) {
     constexpr int RP = 3;
-    hipLaunchKernelGGL((k_glm_family_batched<Link, K, RP>), dim3(grid), dim3(256),
+    hipLaunchKernelGGL((k_glm_family_batched<Stage, K, RP>), dim3(grid), dim3(256),
                        FbGeom<K>::lds_bytes(RP), stream, (const unsigned short*)X, y, offset,
                        n_rows, (const unsigned short*)theta_p, lp, logp_const, out, workspace);
 }
 
-template <class Link, typename... Args>
+template <class Stage, typename... Args>
 static bool dispatch_fb(int K, Args... args) {
     switch (K) {
-        case 8:    launch_fb<Link, 8>(args...); return true;
-        case 16:   launch_fb<Link, 16>(args...); return true;
-        case 32:   launch_fb<Link, 32>(args...); return true;
-        case 64:   launch_fb<Link, 64>(args...); return true;
-        case 128:  launch_fb<Link, 128>(args...); return true;
-        case 256:  launch_fb<Link, 256>(args...); return true;
-        case 512:  launch_fb<Link, 512>(args...); return true;
-        case 1024: launch_fb<Link, 1024>(args...); return true;
+        case 8:    launch_fb<Stage, 8>(args...); return true;
+        case 16:   launch_fb<Stage, 16>(args...); return true;
+        case 32:   launch_fb<Stage, 32>(args...); return true;
+        case 64:   launch_fb<Stage, 64>(args...); return true;
+        case 128:  launch_fb<Stage, 128>(args...); return true;
+        case 256:  launch_fb<Stage, 256>(args...); return true;
+        case 512:  launch_fb<Stage, 512>(args...); return true;
+        case 1024: launch_fb<Stage, 1024>(args...); return true;
         default:   return false;
     }
+}
+
+static bool fb_supported_k(int K) { return K >= 8 && K <= 1024 && (K & (K - 1)) == 0; }
+
+// What the entry points share once their arguments are checked: the grid,
+// the zeroed out, the kernel and the slab reduction.  -3 workspace too small.
+template <class Stage>
+static int fb_run(const void* X, const float* y, const float* offset, long long n_rows, int K,
+                  const void* theta_p, typename Stage::Params lp, double logp_const, double* out,
+                  float* workspace, long long ws_bytes, int blocks_per_cu, hipStream_t stream) {
+    const int row_groups = K >= 128 ? 1 : 4;   // FbGeom<K>::WR
+    const int tile_rows = 32 * row_groups;     // FbGeom<K>::TR
+
+    const long long n_tiles = (n_rows + tile_rows - 1) / tile_rows;
+    int grid = 256 * blocks_per_cu;
+    if (n_tiles < grid) grid = n_tiles < 1 ? 1 : (int)n_tiles;
+    // FED_GLM_BATCHED_GRID caps the grid (tests reach several tiles per
+    // block at small N with it); read per call
+    if (const char* ge = getenv("FED_GLM_BATCHED_GRID")) {
+        const int v = atoi(ge);
+        if (v >= 1 && v < grid) grid = v;
+    }
+    const long long block_bytes = (long long)row_groups * K * FB_CH * sizeof(float);
+    if ((long long)grid * block_bytes > ws_bytes) grid = (int)(ws_bytes / block_bytes);
+    if (grid < 1) return -3;
+
+    const long long out_cols = FB_CH + (long long)K * FB_CH;
+    hipError_t err = hipMemsetAsync(out, 0, out_cols * sizeof(double), stream);
+    if (err != hipSuccess) return (int)err;
+
+    if (!dispatch_fb<Stage>(K, grid, stream, X, y, offset, n_rows, theta_p, lp, logp_const, out,
+                            workspace))
+        return -4;
+    hipError_t kerr = hipGetLastError();
+    if (kerr != hipSuccess) return (int)kerr;
+
+    const int n_slabs = grid * row_groups;
+    const int cols = K * FB_CH;
+    int chunks = n_slabs / 8;
+    if (chunks < 1) chunks = 1;
+    if (chunks > 64) chunks = 64;
+    hipLaunchKernelGGL(k_colsum_reduce, dim3((cols + 255) / 256, chunks), dim3(256), 0, stream,
+                       workspace, n_slabs, cols, out + FB_CH);
+    return (int)hipGetLastError();
 }
 
 extern "C" {
@@ -361,47 +446,42 @@ int fed_glm_family_batched(
 ) {
     hipStream_t stream = (hipStream_t)stream_v;
     if (link != FED_LINK_POISSON && link != FED_LINK_GAUSSIAN) return -5;
-    if (K < 8 || K > 1024 || (K & (K - 1)) != 0) return -4;
-    const int row_groups = K >= 128 ? 1 : 4;   // FbGeom<K>::WR
-    const int tile_rows = 32 * row_groups;     // FbGeom<K>::TR
-
-    const long long n_tiles = (n_rows + tile_rows - 1) / tile_rows;
-    int grid = 256 * fb_blocks_per_cu(K);
-    if (n_tiles < grid) grid = n_tiles < 1 ? 1 : (int)n_tiles;
-    // FED_GLM_BATCHED_GRID caps the grid (tests reach several tiles per
-    // block at small N with it); read per call
-    if (const char* ge = getenv("FED_GLM_BATCHED_GRID")) {
-        const int v = atoi(ge);
-        if (v >= 1 && v < grid) grid = v;
-    }
-    const long long block_bytes = (long long)row_groups * K * FB_CH * sizeof(float);
-    if ((long long)grid * block_bytes > ws_bytes) grid = (int)(ws_bytes / block_bytes);
-    if (grid < 1) return -3;
-
-    const long long out_cols = FB_CH + (long long)K * FB_CH;
-    hipError_t err = hipMemsetAsync(out, 0, out_cols * sizeof(double), stream);
-    if (err != hipSuccess) return (int)err;
-
+    if (!fb_supported_k(K)) return -4;
     const LinkParams lp = make_link_params(sigma);
-    bool ok;
     if (link == FED_LINK_POISSON)
-        ok = dispatch_fb<PoissonLink>(K, grid, stream, X, y_f32, offset_f32, n_rows,
-                                      theta_pieces_bf16, lp, logp_const, out, workspace);
-    else
-        ok = dispatch_fb<GaussianLink>(K, grid, stream, X, y_f32, offset_f32, n_rows,
-                                       theta_pieces_bf16, lp, logp_const, out, workspace);
-    if (!ok) return -4;
-    hipError_t kerr = hipGetLastError();
-    if (kerr != hipSuccess) return (int)kerr;
+        return fb_run<ElementStage<PoissonLink>>(X, y_f32, offset_f32, n_rows, K,
+                                                 theta_pieces_bf16, lp, logp_const, out,
+                                                 workspace, ws_bytes, fb_blocks_per_cu(K), stream);
+    return fb_run<ElementStage<GaussianLink>>(X, y_f32, offset_f32, n_rows, K, theta_pieces_bf16,
+                                              lp, logp_const, out, workspace, ws_bytes,
+                                              fb_blocks_per_cu(K), stream);
+}
 
-    const int n_slabs = grid * row_groups;
-    const int cols = K * FB_CH;
-    int chunks = n_slabs / 8;
-    if (chunks < 1) chunks = 1;
-    if (chunks > 64) chunks = 64;
-    hipLaunchKernelGGL(k_colsum_reduce, dim3((cols + 255) / 256, chunks), dim3(256), 0, stream,
-                       workspace, n_slabs, cols, out + FB_CH);
-    return (int)hipGetLastError();
+// Softmax (multinomial) GLM on the same kernel with the row-coupled
+// SoftmaxStage: the 16 columns are 16/CP chains of CP class slots, CP the
+// next power of two >= n_classes.  y_f32 = fp32[n_rows] holds the labels in
+// [0, n_classes) (exact in f32); theta_pieces_bf16 = bf16[3][16][K] with
+// column g*CP + c the class c of chain g (what the columns of padded
+// classes hold is not read into any result).  out, workspace and the grid
+// as in fed_glm_family_batched: out[0..16) are per-column sums, the logp of
+// chain g is the sum of out[g*CP .. g*CP+CP), and the G columns of padded
+// classes are exactly 0.  Returns -3 workspace too small, -4 unsupported K,
+// -6 n_classes outside [2, 16]; all of them before anything is launched.
+int fed_glm_softmax_batched(
+    const void* X, const float* y_f32, long long n_rows, int K,
+    const void* theta_pieces_bf16, int n_classes,
+    double* out, float* workspace, long long ws_bytes,
+    void* stream_v
+) {
+    hipStream_t stream = (hipStream_t)stream_v;
+    if (!fb_supported_k(K)) return -4;
+    if (n_classes < 2 || n_classes > FB_CH) return -6;
+    SoftmaxParams sp;
+    sp.n_classes = n_classes;
+    sp.cp = 2;
+    while (sp.cp < n_classes) sp.cp *= 2;
+    return fb_run<SoftmaxStage>(X, y_f32, nullptr, n_rows, K, theta_pieces_bf16, sp, 0.0, out,
+                                workspace, ws_bytes, fb_blocks_per_cu(K), stream);
 }
 
 }  // extern "C"
