@@ -173,6 +173,20 @@ def _try_load() -> Optional[ctypes.CDLL]:
         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
         ctypes.c_void_p,
     ]
+    lib.fed_gaussian_persistent_start.restype = ctypes.c_void_p
+    lib.fed_gaussian_persistent_start.argtypes = [
+        ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
+        ctypes.c_double, ctypes.c_int,
+    ]
+    lib.fed_gaussian_persistent_eval.restype = ctypes.c_int
+    lib.fed_gaussian_persistent_eval.argtypes = [
+        ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+        ctypes.POINTER(ctypes.c_double),
+    ]
+    lib.fed_gaussian_persistent_stop.restype = ctypes.c_int
+    lib.fed_gaussian_persistent_stop.argtypes = [ctypes.c_void_p]
+    lib.fed_gaussian_persistent_relaunch_count.restype = ctypes.c_int
+    lib.fed_gaussian_persistent_relaunch_count.argtypes = [ctypes.c_void_p]
     lib.fed_last_hip_error.restype = ctypes.c_char_p
     _lib = lib
     return _lib
@@ -310,6 +324,57 @@ def _require_contiguous(**tensors: torch.Tensor) -> None:
             raise ValueError(f"{name} must be contiguous (strides {t.stride()})")
 
 
+# Argument checks the GLM entry points share.  Pure torch: they run on CPU
+# tensors too (tests/test_ops_arg_checks_cpu.py).  They sit on the host path
+# of every launch, so the passing case does no more than the tests themselves.
+
+def _design_shape(X: torch.Tensor) -> torch.Size:
+    """``(N, K)`` of the design matrix; it must be 2-D."""
+    shape = X.shape
+    if len(shape) != 2:
+        raise ValueError("X must be [N, K]")
+    return shape
+
+
+def _check_design(X: torch.Tensor) -> None:
+    """The kernels read X through data_ptr() as a C-ordered device array, in
+    16-byte vectors."""
+    if not X.is_contiguous():
+        _require_contiguous(X=X)
+    if X.data_ptr() % 16:
+        raise ValueError("X must be 16-byte aligned")
+    if not X.is_cuda:
+        raise ValueError("X must be on a ROCm device")
+
+
+def _check_rows(name: str, t: torch.Tensor, X: torch.Tensor) -> None:
+    """A per-row vector (y, offset): contiguous f32[N] on X's device."""
+    if t.dtype != torch.float32 or t.shape != (X.shape[0],) or t.device != X.device:
+        raise ValueError(f"{name} must be f32[N] on X's device")
+    if not t.is_contiguous():
+        _require_contiguous(**{name: t})
+
+
+def _check_sigma(sigma: float) -> None:
+    if not float(sigma) > 0.0:
+        raise ValueError("sigma must be positive")
+
+
+def _out_buffer(
+    out: Optional[torch.Tensor], shape: Tuple[int, ...], X: torch.Tensor
+) -> torch.Tensor:
+    """``out``, or a new fp64 buffer of ``shape`` on X's device when it is None."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float64, device=X.device)
+    if (
+        out.dtype != torch.float64 or out.shape != shape or out.device != X.device
+        or not out.is_contiguous()
+    ):
+        dims = ", ".join(str(d) for d in shape)
+        raise ValueError(f"out must be a contiguous fp64[{dims}] on X's device")
+    return out
+
+
 def ode_lv_logp_grad(
     u0: torch.Tensor,          # [B, 2] f64
     y_obs: torch.Tensor,       # [n_obs, B, 2] f64
@@ -412,22 +477,6 @@ class PersistentLinearEngine:
 
     def __init__(self, x: torch.Tensor, y: torch.Tensor, sigma: float) -> None:
         lib = require_kernels()
-        if not hasattr(lib.fed_gaussian_persistent_start, "_cfg"):
-            lib.fed_gaussian_persistent_start.restype = ctypes.c_void_p
-            lib.fed_gaussian_persistent_start.argtypes = [
-                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong,
-                ctypes.c_double, ctypes.c_int,
-            ]
-            lib.fed_gaussian_persistent_eval.restype = ctypes.c_int
-            lib.fed_gaussian_persistent_eval.argtypes = [
-                ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
-                ctypes.POINTER(ctypes.c_double),
-            ]
-            lib.fed_gaussian_persistent_stop.restype = ctypes.c_int
-            lib.fed_gaussian_persistent_stop.argtypes = [ctypes.c_void_p]
-            lib.fed_gaussian_persistent_relaunch_count.restype = ctypes.c_int
-            lib.fed_gaussian_persistent_relaunch_count.argtypes = [ctypes.c_void_p]
-            lib.fed_gaussian_persistent_start._cfg = True
         self._lib = lib
         assert x.is_cuda and x.is_contiguous() and y.is_contiguous()
         self._x, self._y = x, y  # keep alive
@@ -526,8 +575,8 @@ def logistic_glm_logp_grad_batched(
     """MFMA-batched evaluation of 16 chains: theta[K,16] -> logp[16], G[K,16].
 
     One pass over X computes Z = X.theta, the per-chain BCE logp, and
-    G = X^T (y - sigmoid(Z)) on the matrix cores (kernel
-    k_logistic_glm_batched).  Per-chain cost ~B x below the single-chain
+    G = X^T (y - sigmoid(Z)) on the matrix cores (the kernels of
+    csrc/glm_logistic_batched.hip).  Per-chain cost ~B x below the single-chain
     kernel -- the multi-chain MCMC axis (reference pm.sample cores=N) on
     one GPU.
     """
@@ -694,36 +743,20 @@ def glm_family_logp_grad(
     lib = require_kernels()
     if link not in GLM_FAMILY_LINKS:
         raise ValueError(f"unknown link {link!r}; expected one of {sorted(GLM_FAMILY_LINKS)}")
-    n, K = X.shape
+    n, K = _design_shape(X)
     if X.dtype not in _GLM_FAMILY_VEC:
         raise TypeError(f"unsupported dtype {X.dtype}")
     if not glm_family_kernel_supports(X.dtype, K):
         raise ValueError(f"family kernel not compiled for (dtype={X.dtype}, K={K})")
-    if not X.is_cuda:
-        raise ValueError("X must be on a ROCm device")
-    if y.dtype != torch.float32 or y.shape != (n,) or y.device != X.device:
-        raise ValueError("y must be f32[N] on X's device")
-    if offset is not None and (
-        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
-    ):
-        raise ValueError("offset must be f32[N] on X's device")
-    if not float(sigma) > 0.0:
-        raise ValueError("sigma must be positive")
-    _require_contiguous(X=X, y=y)
+    _check_sigma(sigma)
+    _check_rows("y", y, X)
     if offset is not None:
-        _require_contiguous(offset=offset)
-    if X.data_ptr() % 16:
-        raise ValueError("X must be 16-byte aligned")
+        _check_rows("offset", offset, X)
+    _check_design(X)
     beta_f32 = beta.detach().to(device=X.device, dtype=torch.float32).contiguous()
     if beta_f32.shape != (K,):
         raise ValueError(f"beta must have shape ({K},), got {tuple(beta_f32.shape)}")
-    if out is None:
-        out = torch.empty(1 + K, dtype=torch.float64, device=X.device)
-    elif (
-        out.dtype != torch.float64 or out.shape != (1 + K,) or out.device != X.device
-        or not out.is_contiguous()
-    ):
-        raise ValueError(f"out must be a contiguous fp64[{1 + K}] on X's device")
+    out = _out_buffer(out, (1 + K,), X)
     ws = _workspace(X.device, f"glm_family{K}", 1024 * K, dtype=torch.float32)
     rc = lib.fed_glm_family(
         X.data_ptr(), y.data_ptr(), offset.data_ptr() if offset is not None else None,
@@ -799,37 +832,21 @@ def glm_family_logp_grad_batched(
         raise ValueError(
             f"unknown link {link!r}; expected one of {sorted(_GLM_FAMILY_BATCHED_LINKS)}"
         )
-    n, K = X.shape
+    n, K = _design_shape(X)
     B = BATCH_CHAINS
     if X.dtype != torch.bfloat16:
         raise TypeError(f"unsupported dtype {X.dtype}: the batched family kernel reads bf16 X")
     if not glm_family_batched_supports(X.dtype, K):
         raise ValueError(f"batched family kernel not compiled for (dtype={X.dtype}, K={K})")
-    if not X.is_cuda:
-        raise ValueError("X must be on a ROCm device")
-    if y.dtype != torch.float32 or y.shape != (n,) or y.device != X.device:
-        raise ValueError("y must be f32[N] on X's device")
-    if offset is not None and (
-        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
-    ):
-        raise ValueError("offset must be f32[N] on X's device")
-    if not float(sigma) > 0.0:
-        raise ValueError("sigma must be positive")
-    _require_contiguous(X=X, y=y)
+    _check_sigma(sigma)
+    _check_rows("y", y, X)
     if offset is not None:
-        _require_contiguous(offset=offset)
-    if X.data_ptr() % 16:
-        raise ValueError("X must be 16-byte aligned")
+        _check_rows("offset", offset, X)
+    _check_design(X)
     if tuple(theta.shape) != (K, B):
         raise ValueError(f"theta must be [{K}, {B}], got {tuple(theta.shape)}")
     pieces = split_bf16x3(theta.to(device=X.device))
-    if out is None:
-        out = torch.empty(B + K * B, dtype=torch.float64, device=X.device)
-    elif (
-        out.dtype != torch.float64 or out.shape != (B + K * B,) or out.device != X.device
-        or not out.is_contiguous()
-    ):
-        raise ValueError(f"out must be a contiguous fp64[{B + K * B}] on X's device")
+    out = _out_buffer(out, (B + K * B,), X)
     ws = _workspace(X.device, "glm_family_batched", _GLM_FAMILY_BATCHED_WS, dtype=torch.float32)
     rc = lib.fed_glm_family_batched(
         X.data_ptr(), y.data_ptr(), offset.data_ptr() if offset is not None else None,
@@ -893,30 +910,19 @@ def glm_softmax_logp_grad(
     ``out[:16]`` over each class group.
     """
     lib = require_kernels()
-    n, K = X.shape
+    n, K = _design_shape(X)
     B = BATCH_CHAINS
     if X.dtype != torch.bfloat16:
         raise TypeError(f"unsupported dtype {X.dtype}: the softmax kernel reads bf16 X")
     if not glm_family_batched_supports(X.dtype, K):
         raise ValueError(f"softmax kernel not compiled for (dtype={X.dtype}, K={K})")
     cp = glm_softmax_class_group(n_classes)
-    if not X.is_cuda:
-        raise ValueError("X must be on a ROCm device")
-    if y.dtype != torch.float32 or y.shape != (n,) or y.device != X.device:
-        raise ValueError("y must be f32[N] on X's device")
-    _require_contiguous(X=X, y=y)
-    if X.data_ptr() % 16:
-        raise ValueError("X must be 16-byte aligned")
+    _check_rows("y", y, X)
+    _check_design(X)
     if tuple(theta16.shape) != (K, B):
         raise ValueError(f"theta16 must be [{K}, {B}], got {tuple(theta16.shape)}")
     pieces = split_bf16x3(theta16.to(device=X.device))
-    if out is None:
-        out = torch.empty(B + K * B, dtype=torch.float64, device=X.device)
-    elif (
-        out.dtype != torch.float64 or out.shape != (B + K * B,) or out.device != X.device
-        or not out.is_contiguous()
-    ):
-        raise ValueError(f"out must be a contiguous fp64[{B + K * B}] on X's device")
+    out = _out_buffer(out, (B + K * B,), X)
     ws = _workspace(X.device, "glm_softmax", _GLM_FAMILY_BATCHED_WS, dtype=torch.float32)
     rc = lib.fed_glm_softmax_batched(
         X.data_ptr(), y.data_ptr(), n, K, pieces.data_ptr(), int(n_classes),
@@ -969,37 +975,20 @@ def glm_family_fisher(
         raise ValueError(
             f"unknown link {link!r}; expected one of {sorted(_GLM_FAMILY_BATCHED_LINKS)}"
         )
-    if X.dim() != 2:
-        raise ValueError("X must be [N, K]")
-    n, K = X.shape
+    n, K = _design_shape(X)
     if X.dtype != torch.bfloat16:
         raise TypeError(f"unsupported dtype {X.dtype}: the Fisher kernel reads bf16 X")
     if not glm_family_fisher_supports(X.dtype, K):
         raise ValueError(f"Fisher kernel not compiled for (dtype={X.dtype}, K={K})")
-    if not float(sigma) > 0.0:
-        raise ValueError("sigma must be positive")
+    _check_sigma(sigma)
     if tuple(beta.shape) != (K,):
         raise ValueError(f"beta must have shape ({K},), got {tuple(beta.shape)}")
-    if offset is not None and (
-        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
-    ):
-        raise ValueError("offset must be f32[N] on X's device")
-    _require_contiguous(X=X)
     if offset is not None:
-        _require_contiguous(offset=offset)
-    if not X.is_cuda:
-        raise ValueError("X must be on a ROCm device")
-    if X.data_ptr() % 16:
-        raise ValueError("X must be 16-byte aligned")
-    if out is not None and (
-        out.dtype != torch.float64 or out.shape != (K, K) or out.device != X.device
-        or not out.is_contiguous()
-    ):
-        raise ValueError(f"out must be a contiguous fp64[{K}, {K}] on X's device")
+        _check_rows("offset", offset, X)
+    _check_design(X)
+    out = _out_buffer(out, (K, K), X)
     lib = require_kernels()
     beta_f32 = beta.detach().to(device=X.device, dtype=torch.float32).contiguous()
-    if out is None:
-        out = torch.empty((K, K), dtype=torch.float64, device=X.device)
     w_elems = 4 * ((n + 3) // 4) if K > 128 else 0
     ws = _workspace(
         X.device, "glm_family_fisher", _GLM_FAMILY_FISHER_SLAB + w_elems, dtype=torch.float32
@@ -1026,40 +1015,23 @@ def _glm_family_fvp(
     """What the product and the diagonal share: ``v is None`` is the diagonal."""
     if link not in GLM_FAMILY_LINKS:
         raise ValueError(f"unknown link {link!r}; expected one of {sorted(GLM_FAMILY_LINKS)}")
-    if X.dim() != 2:
-        raise ValueError("X must be [N, K]")
-    n, K = X.shape
+    n, K = _design_shape(X)
     if X.dtype not in _GLM_FAMILY_VEC:
         raise TypeError(f"unsupported dtype {X.dtype}")
     if not glm_family_kernel_supports(X.dtype, K):
         raise ValueError(f"family kernel not compiled for (dtype={X.dtype}, K={K})")
-    if not float(sigma) > 0.0:
-        raise ValueError("sigma must be positive")
+    _check_sigma(sigma)
     if tuple(beta.shape) != (K,):
         raise ValueError(f"beta must have shape ({K},), got {tuple(beta.shape)}")
     if v is not None and tuple(v.shape) != (K,):
         raise ValueError(f"v must have shape ({K},), got {tuple(v.shape)}")
-    if offset is not None and (
-        offset.dtype != torch.float32 or offset.shape != (n,) or offset.device != X.device
-    ):
-        raise ValueError("offset must be f32[N] on X's device")
-    _require_contiguous(X=X)
     if offset is not None:
-        _require_contiguous(offset=offset)
-    if not X.is_cuda:
-        raise ValueError("X must be on a ROCm device")
-    if X.data_ptr() % 16:
-        raise ValueError("X must be 16-byte aligned")
-    if out is not None and (
-        out.dtype != torch.float64 or out.shape != (K,) or out.device != X.device
-        or not out.is_contiguous()
-    ):
-        raise ValueError(f"out must be a contiguous fp64[{K}] on X's device")
+        _check_rows("offset", offset, X)
+    _check_design(X)
+    out = _out_buffer(out, (K,), X)
     lib = require_kernels()
     beta_f32 = beta.detach().to(device=X.device, dtype=torch.float32).contiguous()
     v_f32 = None if v is None else v.detach().to(device=X.device, dtype=torch.float32).contiguous()
-    if out is None:
-        out = torch.empty(K, dtype=torch.float64, device=X.device)
     # a slab of its own: glm_family_logp_grad's may be in use on another stream
     ws = _workspace(X.device, f"glm_family_fvp{K}", 1024 * K, dtype=torch.float32)
     rc = lib.fed_glm_family_fvp(

@@ -233,3 +233,18 @@ static inline int pick_grid(long long work_items, int block) {
     if (blocks < 1) blocks = 1;
     return (int)blocks;
 }
+
+// Sum the fp32 slab [n_slabs][cols] into out[cols] with k_colsum_reduce: one
+// y-chunk of the grid per 8 slab rows, 1..64 of them.  `out` must already be
+// zeroed (with more than one chunk the kernel accumulates by atomics); the
+// memset stays with the caller, whose main kernel may have added into `out`
+// after it.  Returns hipGetLastError().
+static inline int launch_colsum_reduce(const float* slab, int n_slabs, int cols, double* out,
+                                       hipStream_t stream) {
+    int chunks = n_slabs / 8;
+    if (chunks < 1) chunks = 1;
+    if (chunks > 64) chunks = 64;
+    hipLaunchKernelGGL(k_colsum_reduce, dim3((cols + 255) / 256, chunks), dim3(256), 0, stream,
+                       slab, n_slabs, cols, out);
+    return (int)hipGetLastError();
+}

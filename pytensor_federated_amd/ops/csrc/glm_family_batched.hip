@@ -63,7 +63,7 @@
 // offset (f32) into LDS | barrier | phase A from LDS, partial Z to LDS |
 // barrier | one thread per (row, chain) slot: z, Stage::eval, fp64 logp,
 // residual pieces to LDS (R^T image [piece][chain][row]) | barrier | phase
-// B: X^T fragments by the u16 LDS gather of the v1/v2 logistic kernels |
+// B: X^T fragments by the u16 LDS gather of the v2 logistic kernel |
 // barrier.  X is read from HBM exactly once.
 //
 // Ragged tiles.  Rows at or past n_rows are zero-filled by a conditional
@@ -417,14 +417,7 @@ static int fb_run(const void* X, const float* y, const float* offset, long long 
     hipError_t kerr = hipGetLastError();
     if (kerr != hipSuccess) return (int)kerr;
 
-    const int n_slabs = grid * row_groups;
-    const int cols = K * FB_CH;
-    int chunks = n_slabs / 8;
-    if (chunks < 1) chunks = 1;
-    if (chunks > 64) chunks = 64;
-    hipLaunchKernelGGL(k_colsum_reduce, dim3((cols + 255) / 256, chunks), dim3(256), 0, stream,
-                       workspace, n_slabs, cols, out + FB_CH);
-    return (int)hipGetLastError();
+    return launch_colsum_reduce(workspace, grid * row_groups, K * FB_CH, out + FB_CH, stream);
 }
 
 extern "C" {

@@ -362,13 +362,7 @@ int fed_glm_family_fvp(
     hipError_t kerr = hipGetLastError();
     if (kerr != hipSuccess) return (int)kerr;
 
-    const int rgrid = (K + 255) / 256;
-    int chunks = grid / 8;
-    if (chunks < 1) chunks = 1;
-    if (chunks > 64) chunks = 64;
-    hipLaunchKernelGGL(k_colsum_reduce, dim3(rgrid, chunks), dim3(256), 0, stream,
-                       workspace, grid, K, out);
-    return (int)hipGetLastError();
+    return launch_colsum_reduce(workspace, grid, K, out, stream);
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // Batched (16-chain) logistic GLM on CDNA4 (gfx950) matrix cores: the MFMA
 // fragment-map probe, the kernels that ship (v3 at K=1024, v2 at K=512, v3s
-// as an opt-in), two A/B baselines (v1, whole-tile LDS) and their
-// dispatcher.  Every kernel here is covered by the exact-probe tests.
-// Shared pieces and the overview of the GLM units are in fed_common.hpp.
+// as an opt-in), one A/B baseline (whole-tile LDS) and their dispatcher.
+// Every kernel here is covered by the exact-probe tests.  Shared pieces and
+// the overview of the GLM units are in fed_common.hpp.
 //
 // History (ms at 2e6 x 1024 x 16 bf16, profiles/PROFILES.md): v1, a
 // double-buffered chunk pipeline that re-reads X for phase B, 1.568; v2,
@@ -13,7 +13,8 @@
 // default.  The LDS-resident whole-tile variant lost its round-1 A/B to v1
 // (no figure recorded).  The scalar-gather image of v3, its instrumented
 // build and the two environment flags that selected them last exist at
-// commit 5e9376b.
+// commit 5e9376b.  v1 and the flag that selected it (FED_BATCHED_V1) last
+// exist at commit ebb4f6a.
 
 #include "fed_common.hpp"
 
@@ -70,14 +71,14 @@ extern "C" int fed_mfma_probe(const void* A, const void* B, void* D, void* strea
 //     R[rows,16]  = y - sigmoid(Z)
 //     G[K,16]    += X^T[K,rows] . R[rows,16]       (phase B, MFMA)
 //
-// X is HBM-read once per call (v1/v2: k-chunks staged to LDS, phase B
+// X is HBM-read once per call (v2: k-chunks staged to LDS, phase B
 // re-reads the L2-hot chunk; v3/v3s: the tile stays in LDS throughout); at
 // B=16 the arithmetic is 4*N*K*B flops -- VALU could not keep up with the
 // HBM stream (0.8 TFLOP/call vs ~4 ms of traffic), MFMA makes compute a
 // ~10% bystander.  Per-chain cost is ~B x lower than the single-chain
 // kernel.
 //
-// Geometry: block = 256 threads = 4 waves.  v1/v2: row tile 64 (16 rows/wave
+// Geometry: block = 256 threads = 4 waves.  v2: row tile 64 (16 rows/wave
 // in phase A); K chunked by 128 (each wave owns a 32-col slice in phase B).
 // v3/v3s: row tile 32, every wave owns a K slice in both phases.  G
 // accumulates in AGPRs (16 tiles x 4 f32/lane/wave at K=1024); per-block
@@ -88,8 +89,8 @@ extern "C" int fed_mfma_probe(const void* A, const void* B, void* D, void* strea
 // B[k=(l>>4)*8+j][j=l&15], D[col=l&15][row=(l>>4)*4+r].
 
 #define BCH 16           // chains per call
-#define BL_ROWS 64       // rows per block tile
-#define BL_CHUNK 128     // K columns per staged chunk
+#define BL_ROWS 64       // rows per block tile (v2, whole-tile LDS)
+#define BL_CHUNK 128     // K columns per chunk (v2, whole-tile LDS)
 #define XPAD 8           // X_lds row pad (elems): stride 272 B, b128-clean
 #define TPAD 8           // Theta row pad: stride 2064+16 B
 #define RPAD 8           // R_T row pad: stride 144 B
@@ -137,15 +138,42 @@ __device__ __forceinline__ float* epilogue_logp(float* slab, float* red_lds, flo
     return slab_blk + BCH;
 }
 
-// v1/v2 chunk staging: a thread owns rows {st_r0 + 16 rr}, one 16-B group
-// each.  The loads are issued as one group of four so that four register
-// quads stay in flight, and edge rows zero-fill by the CONDITIONAL form
-// (both: see the v2 notes).  Macros, not functions: a function form
-// (U4 (&ld)[4] by reference) compiled to a different instruction mix in
-// all four instantiations, and this code is compiler-sensitive.  They use
-// the kernel's X, n_rows, row0, st_r0, ld, x_lds, x_buf and x_stride;
-// `k0` is the thread's column within chunk `c`, `lds_col` its (possibly
-// swizzled) column in the LDS row of buffer `buf`.
+// ---------------------------------------------------------------------------
+// Batched logistic v2: double-buffered chunk pipeline, swizzled LDS
+// ---------------------------------------------------------------------------
+// A 64-row tile is walked in 128-column chunks through two LDS buffers,
+// over BOTH phases: phase A consumes chunks 0..n-1 (Z), phase B consumes
+// them again in reverse (G), re-reading X through L2.  One barrier per
+// chunk step.  What the measurements fixed (profiles/PROFILES.md; the
+// unswizzled forward-walking predecessor measured 1.57 ms, with 10.8% LDS
+// bank-conflict cycles from the phase-B transposed u16 reads: rows r/r+8
+// land on one bank at the 16B-aligned row stride):
+//
+//  * load placement: chunk c+1's global loads are issued BEFORE chunk c's
+//    MFMAs and written to LDS after them.  That forces the allocator to keep
+//    four load register quads alive across the MFMAs, so four loads are in
+//    flight.  A write-after-barrier variant (load c+2 right after the
+//    staging write) was tried and REVERTED: hipcc coalesced the 4 staging
+//    loads into one register quad with a serial s_waitcnt vmcnt(0) per load
+//    -- serial HBM round trips, 2.8 ms vs 1.57.
+//  * XOR swizzle of the 16-byte group index, key = ((row>>3)&1)<<1 --
+//    rows r and r+8 (the colliding pair within a 32-lane half) get their
+//    group-bit-1 flipped against each other, separating their banks for
+//    the phase-B scalar reads while leaving the b128 write/read patterns
+//    near-conflict-free.
+//  * edge rows zero-fill by the CONDITIONAL form (zero, then load if the
+//    row is in range): an address-clamp variant (branch-free) made hipcc
+//    spill the staged loads to scratch with a vmcnt(0) after EACH -- serial
+//    HBM round trips (2.8 ms).  With the conditional form the 4 loads stay
+//    in 4 register quads, in flight together (verified in the ISA).
+//
+// Chunk staging: a thread owns rows {st_r0 + 16 rr}, one 16-B group each,
+// loaded as one group of four and zero-filled conditionally (both: above).
+// Macros, not functions: a function form (U4 (&ld)[4] by reference)
+// compiled to a different instruction mix in both instantiations, and this
+// code is compiler-sensitive.  They use the kernel's X, n_rows, row0, st_r0,
+// ld, x_lds, x_buf and x_stride; `k0` is the thread's column within chunk
+// `c`, `lds_col` its swizzled column in the LDS row of buffer `buf`.
 #define BL_LOAD_CHUNK(c, k0)                                                    \
     _Pragma("unroll") for (int rr = 0; rr < 4; ++rr) {                          \
         const long long row = row0 + st_r0 + rr * 16;                           \
@@ -159,169 +187,6 @@ __device__ __forceinline__ float* epilogue_logp(float* slab, float* red_lds, flo
 
 template <int K>  // compile-time K: keeps g_acc statically indexed (no
                   // scratch spill -- cdna_hip_programming.md rule 20)
-__global__ __launch_bounds__(256) void k_logistic_glm_batched(
-    const unsigned short* __restrict__ X,   // [N][K] bf16
-    const unsigned short* __restrict__ y,   // [N] bf16
-    long long n_rows,
-    const unsigned short* __restrict__ theta_t,  // [BCH][K] bf16 (transposed!)
-    float* __restrict__ slab                     // [grid][BCH + K*BCH]
-) {
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    constexpr int n_chunks = K / BL_CHUNK;
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    unsigned short* th_lds = (unsigned short*)smem;                 // [BCH][K+TPAD]
-    const int th_stride = K + TPAD;
-    unsigned short* x_lds = th_lds + BCH * th_stride;               // [2][BL_ROWS][BL_CHUNK+XPAD]
-    const int x_stride = BL_CHUNK + XPAD;
-    const int x_buf = BL_ROWS * x_stride;
-    unsigned short* rt_lds = x_lds + 2 * x_buf;                     // [BCH][BL_ROWS+RPAD]
-    const int rt_stride = BL_ROWS + RPAD;
-    float* y_lds = (float*)(rt_lds + BCH * rt_stride + 8);          // [BL_ROWS]
-    float* red_lds = y_lds + BL_ROWS;                               // [256]
-
-    // ---- stage Theta^T once per block ----
-    for (int idx = threadIdx.x * 8; idx < BCH * K; idx += 256 * 8) {
-        const int b = idx / K;
-        const int k = idx % K;
-        *(U4*)&th_lds[b * th_stride + k] = *(const U4*)&theta_t[b * K + k];
-    }
-
-    f32x4_t g_acc[n_chunks * 2];
-#pragma unroll
-    for (int t = 0; t < n_chunks * 2; ++t) g_acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    float logp_acc = 0.f;  // this lane's chain partial (chain = lane&15)
-
-    // staging helpers: thread owns rows {r0, r0+16, r0+32, r0+48}, 16 B each
-    const int st_r0 = threadIdx.x / 16;          // 0..15
-    const int st_k0 = (threadIdx.x % 16) * (BL_CHUNK / 16);
-
-    const long long n_tiles = (n_rows + BL_ROWS - 1) / BL_ROWS;
-    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const long long row0 = tile * BL_ROWS;
-        if (threadIdx.x < BL_ROWS) {
-            const long long r = row0 + threadIdx.x;
-            y_lds[threadIdx.x] = r < n_rows ? bf16_bits_to_f32(y[r]) : 0.f;
-        }
-
-        // double-buffered chunk pipeline over BOTH phases: phase A consumes
-        // chunks 0..n-1 (Z), phase B consumes them again (G).  One barrier
-        // per step; next chunk's global loads issue before the MFMAs.
-        U4 ld[4];
-
-        BL_LOAD_CHUNK(0, st_k0)
-        BL_WRITE_CHUNK(0, st_k0)
-        int cur = 0;
-
-        // ---- phase A: Z = X . Theta ----
-        f32x4_t z_acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < n_chunks; ++c) {
-            __syncthreads();  // buf[cur] (and Theta on c==0) visible
-            if (c + 1 < n_chunks) BL_LOAD_CHUNK(c + 1, st_k0)
-#pragma unroll
-            for (int ks = 0; ks < BL_CHUNK / 32; ++ks) {
-                frag_u a, b;
-                const int arow = wid * 16 + (lane & 15);
-                const int ak = ks * 32 + (lane >> 4) * 8;
-                a.q = *(U4*)&x_lds[cur * x_buf + arow * x_stride + ak];
-                const int bk = c * BL_CHUNK + ks * 32 + (lane >> 4) * 8;
-                b.q = *(U4*)&th_lds[(lane & 15) * th_stride + bk];
-                z_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, z_acc, 0, 0, 0);
-            }
-            if (c + 1 < n_chunks) BL_WRITE_CHUNK(cur ^ 1, st_k0)
-            cur ^= 1;
-        }
-
-        // ---- logp + R from Z (also prefetch chunk 0 for phase B) ----
-        BL_LOAD_CHUNK(0, st_k0)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row_in_wave = (lane >> 4) * 4 + r;
-            const int row_in_tile = wid * 16 + row_in_wave;
-            const long long row = row0 + row_in_tile;
-            const int chain = lane & 15;
-            float z = z_acc[r];
-            float yv = y_lds[row_in_tile];
-            float resid = 0.f;
-            if (row < n_rows) resid = logistic_term_resid(z, yv, logp_acc);
-            rt_lds[chain * rt_stride + row_in_tile] = f32_to_bf16_rne_bits(resid);
-        }
-        __syncthreads();  // R complete; x_lds free
-        BL_WRITE_CHUNK(0, st_k0)
-        cur = 0;
-
-        // ---- phase B: G += X_chunk^T . R (chunks are L2-hot) ----
-#pragma unroll
-        for (int c = 0; c < n_chunks; ++c) {
-            __syncthreads();
-            if (c + 1 < n_chunks) BL_LOAD_CHUNK(c + 1, st_k0)
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) {
-                const int kcol0 = wid * 32 + t2 * 16;
-                f32x4_t acc = g_acc[c * 2 + t2];
-#pragma unroll
-                for (int rs = 0; rs < 2; ++rs) {
-                    frag_u a, b;
-                    const int kcol = kcol0 + (lane & 15);
-                    const int arow0 = rs * 32 + (lane >> 4) * 8;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        a.u[j] = x_lds[cur * x_buf + (arow0 + j) * x_stride + kcol];
-                    b.q = *(U4*)&rt_lds[(lane & 15) * rt_stride + rs * 32 + (lane >> 4) * 8];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc, 0, 0, 0);
-                }
-                g_acc[c * 2 + t2] = acc;
-            }
-            if (c + 1 < n_chunks) BL_WRITE_CHUNK(cur ^ 1, st_k0)
-            cur ^= 1;
-        }
-        __syncthreads();  // rt_lds reuse next tile
-    }
-
-    // ---- epilogue: block partials -> slab ----
-    float* g_slab = epilogue_logp<K>(slab, red_lds, logp_acc);
-#pragma unroll
-    for (int c = 0; c < n_chunks; ++c) {
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kcol = c * BL_CHUNK + wid * 32 + t2 * 16 + (lane >> 4) * 4 + r;
-                const int chain = lane & 15;
-                g_slab[(long long)kcol * BCH + chain] = g_acc[c * 2 + t2][r];
-            }
-        }
-    }
-}
-
-
-// ---------------------------------------------------------------------------
-// Batched logistic v2: fewer barriers, swizzled LDS, write-after-barrier
-// ---------------------------------------------------------------------------
-// Round-1 PMC on v1 (profiles/PROFILES.md): 60% wave-park cycles (staging
-// written BEFORE each chunk barrier, loads only get the MFMA span) and
-// 10.8% LDS bank-conflict cycles (phase-B transposed u16 reads: rows r/r+8
-// land on one bank at the 16B-aligned row stride).  v2 changes:
-//
-//  * (a write-after-barrier staging variant was tried and REVERTED: hipcc
-//    coalesced the 4 staging loads into one register quad with a serial
-//    vmcnt(0) per load -- 2.8 ms vs 1.57.  v1's load placement, chunk
-//    c+1's loads issued before chunk c's MFMAs, is what keeps 4 loads in
-//    flight under this compiler.)
-//  * XOR swizzle of the 16-byte group index, key = ((row>>3)&1)<<1 --
-//    rows r and r+8 (the colliding pair within a 32-lane half) get their
-//    group-bit-1 flipped against each other, separating their banks for
-//    the phase-B scalar reads while leaving the b128 write/read patterns
-//    near-conflict-free.
-//  * edge rows keep v1's conditional zero-fill: an address-clamp variant
-//    (branch-free) made hipcc spill the staged loads to scratch with a
-//    vmcnt(0) after EACH -- serial HBM round trips (2.8 ms).  With the
-//    conditional form the 4 loads stay in 4 register quads, in flight
-//    together (verified in the ISA).
-
-template <int K>
 __global__ __launch_bounds__(256) void k_logistic_glm_batched_v2(
     const unsigned short* __restrict__ X,   // [N][K] bf16
     const unsigned short* __restrict__ y,   // [N] bf16
@@ -347,7 +212,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v2(
     // Theta^T staged once per block (a theta read from global inside the
     // MFMA loop poisons the vmcnt pipeline: its wait is FIFO-ordered after
     // the chunk-prefetch loads, so every chunk step drained its prefetch --
-    // measured 2.97 ms vs 1.56 ms v1 before this was reverted to LDS)
+    // measured 2.97 ms vs 1.56 ms with Theta in LDS, and reverted)
     for (int idx = threadIdx.x * 8; idx < BCH * K; idx += 256 * 8) {
         const int b = idx / K;
         const int k = idx % K;
@@ -382,13 +247,9 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v2(
         int cur = 0;
 
         // ---- phase A: Z = X . Theta ----
-        // v1's load placement is kept deliberately: issuing chunk c+1's
-        // loads BEFORE the MFMAs forces the allocator to keep 4 separate
-        // load register sets alive across them (4 loads in flight).  A
-        // write-after-barrier variant (load c+2 right after the staging
-        // write) let hipcc coalesce all 4 loads into ONE register quad
-        // with s_waitcnt vmcnt(0) after EACH -- serial HBM round trips,
-        // measured 2.81 ms vs 1.57 (see git history).
+        // The load placement is deliberate (see the notes above the
+        // kernel): chunk c+1's loads go out BEFORE chunk c's MFMAs, the
+        // LDS write follows them, and that keeps 4 loads in flight.
         f32x4_t z_acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int c = 0; c < n_chunks; ++c) {
@@ -467,7 +328,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v2(
         __syncthreads();  // rt_lds reuse next tile
     }
 
-    // ---- epilogue: block partials -> slab (same layout as v1) ----
+    // ---- epilogue: block partials -> slab ----
     float* g_slab = epilogue_logp<K>(slab, red_lds, logp_acc);
 #pragma unroll
     for (int c = 0; c < n_chunks; ++c) {
@@ -496,7 +357,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v2(
 // the problem's tail tile is processed outside the counted pipeline.
 //
 // Two LDS images.  v3 (K=1024) stores [4][16] subtiles for the hardware
-// transpose read (v4_img below).  v3s (K=512) stores swizzled rows, one
+// transpose read (tr_img below).  v3s (K=512) stores swizzled rows, one
 // 1-KB DMA per row: the pad-free image (row stride 512 u16 == 0 mod 64
 // dwords) would put every row on the same banks, so the SOURCE column
 // group of each lane is XOR-permuted by key(row) = rotl4_by2(row & 15):
@@ -603,7 +464,7 @@ __device__ __forceinline__ void v3_stage_half(
 // (v3_stage_half: one per valid row), so the kernel keeps the tail tile
 // out of the counted pipeline.  Lane n supplies the source of
 // image element n*8: subtile s = n>>3, row j = (n&7)>>1, col-half h = n&1.
-__device__ __forceinline__ void v4_stage_half(
+__device__ __forceinline__ void tr_stage_half(
     const unsigned short* __restrict__ X, long long n_rows, int K,
     long long row0, int colbase, unsigned short* half_buf,
     const char* smem_base, int wid, int lane, int nt_on
@@ -819,7 +680,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3s(
 // group hands lane (l&15) COLUMN l&15 of the 64-elem tile its addresses
 // cover, elems {base + (l&15) + 16j}).  Element offset of (row, col)
 // within a 32-row x 512-col half:
-__device__ __forceinline__ int v4_img(int row, int col) {
+__device__ __forceinline__ int tr_img(int row, int col) {
     return (((row >> 2) * 32 + (col >> 4)) << 6) + ((row & 3) << 4) + (col & 15);
 }
 
@@ -895,8 +756,8 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
         if (pass) V3_BARRIER();
         // prologue: stage tile p_begin fully.  h0 buffers alternate 0/2,
         // h1 lives in buffer 1.
-        v4_stage_half(X, n_rows, K, p_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
-        v4_stage_half(X, n_rows, K, p_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane,
+        tr_stage_half(X, n_rows, K, p_begin * V3_ROWS, 0, x_base, smem, wid, lane, nt_on);
+        tr_stage_half(X, n_rows, K, p_begin * V3_ROWS, V3_HALF, x_base + HBUF, smem, wid, lane,
                       nt_on);
         // the tail tile's short halves cannot be counted: drain them here,
         // which makes its gate [1] trivially true
@@ -925,7 +786,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
             const unsigned yb1 = v3_load_y_asm(y + (yr1 > ymax ? ymax : yr1));
             // [2] prefetch next tile's h0 as deep as possible
             if (more)
-                v4_stage_half(X, n_rows, K, row0 + V3_ROWS, 0, h0n, smem, wid, lane, nt_on);
+                tr_stage_half(X, n_rows, K, row0 + V3_ROWS, 0, h0n, smem, wid, lane, nt_on);
 
             // ---- phase A on h0: z += X[:, w*128 .. +128) . theta ----
             f32x4_t z0 = {0.f, 0.f, 0.f, 0.f}, z1 = {0.f, 0.f, 0.f, 0.f};
@@ -936,8 +797,8 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                 const int g = (kc >> 3) + (lane >> 4);  // 16B group in half
                 const int arow0 = lane & 15;            // rows 0..15
                 const int arow1 = 16 + (lane & 15);     // rows 16..31
-                a0.q = *(U4*)&h0[v4_img(arow0, g * 8)];
-                a1.q = *(U4*)&h0[v4_img(arow1, g * 8)];
+                a0.q = *(U4*)&h0[tr_img(arow0, g * 8)];
+                a1.q = *(U4*)&h0[tr_img(arow1, g * 8)];
                 const int bk = kc + (lane >> 4) * 8;    // theta col (h0)
                 b0f.q = *(U4*)&th_lds[(lane & 15) * th_stride + bk];
                 z0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0.v, b0f.v, z0, 0, 0, 0);
@@ -960,8 +821,8 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                 const int g = (kc >> 3) + (lane >> 4);
                 const int arow0 = lane & 15;
                 const int arow1 = 16 + (lane & 15);
-                a0.q = *(U4*)&h1[v4_img(arow0, g * 8)];
-                a1.q = *(U4*)&h1[v4_img(arow1, g * 8)];
+                a0.q = *(U4*)&h1[tr_img(arow0, g * 8)];
+                a1.q = *(U4*)&h1[tr_img(arow1, g * 8)];
                 const int bk = V3_HALF + kc + (lane >> 4) * 8;  // theta col (h1)
                 bf.q = *(U4*)&th_lds[(lane & 15) * th_stride + bk];
                 z0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0.v, bf.v, z0, 0, 0, 0);
@@ -1008,9 +869,9 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                 // two hardware transpose reads: lane (l&15) gets column
                 // kc+(l&15) for rows (l>>4)*8..+3 and +4..+7
                 const unsigned base0 = (unsigned)((const char*)&h1[
-                    v4_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
+                    tr_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
                 const unsigned base1 = (unsigned)((const char*)&h1[
-                    v4_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
+                    tr_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
                 unsigned long long v0, v1;
                 asm volatile(
                     "ds_read_b64_tr_b16 %0, %2\n\t"
@@ -1026,7 +887,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
             V3_BARRIER();  // everyone done reading h1
             // [6] refill h1 with the NEXT tile's second half
             if (more)
-                v4_stage_half(X, n_rows, K, row0 + V3_ROWS, V3_HALF, h1, smem, wid, lane, nt_on);
+                tr_stage_half(X, n_rows, K, row0 + V3_ROWS, V3_HALF, h1, smem, wid, lane, nt_on);
 
             // ---- phase B, h0 columns ----
 #pragma unroll
@@ -1036,9 +897,9 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
                 frag_u a, b;
                 // two hardware transpose reads, as for h1
                 const unsigned base0 = (unsigned)((const char*)&h0[
-                    v4_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
+                    tr_img((lane >> 4) * 8, kc)] - smem) + (lane & 15) * 8u;
                 const unsigned base1 = (unsigned)((const char*)&h0[
-                    v4_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
+                    tr_img((lane >> 4) * 8 + 4, kc)] - smem) + (lane & 15) * 8u;
                 unsigned long long v0, v1;
                 asm volatile(
                     "ds_read_b64_tr_b16 %0, %2\n\t"
@@ -1055,7 +916,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
         }
     }
 
-    // ---- epilogue: block partials -> slab (layout shared with v1/v2) ----
+    // ---- epilogue: block partials -> slab (layout shared with v2) ----
     // the two slots of one thread are chains (t&15) and ((t+256)&15) == same
     // chain, different rows -- so the plain per-chain strided sum works
     __syncthreads();
@@ -1201,21 +1062,6 @@ __global__ __launch_bounds__(256, 1) void k_logistic_glm_batched_lds(
     }
 }
 
-// slab [grid][slab_cols] fp32 -> out[slab_cols] fp64 (zeroed first: the
-// reduce kernel accumulates with atomics when it runs more than one chunk)
-static int reduce_slab(const float* slab, int grid, long long slab_cols, double* out,
-                       hipStream_t stream) {
-    const int rgrid = ((int)slab_cols + 255) / 256;
-    int chunks = grid / 8;
-    if (chunks < 1) chunks = 1;
-    if (chunks > 64) chunks = 64;
-    hipError_t merr = hipMemsetAsync(out, 0, slab_cols * 8, stream);
-    if (merr != hipSuccess) return (int)merr;
-    hipLaunchKernelGGL(k_colsum_reduce, dim3(rgrid, chunks), dim3(256), 0, stream,
-                       slab, grid, (int)slab_cols, out);
-    return (int)hipGetLastError();
-}
-
 static bool env_flag(const char* name, bool dflt) {
     const char* e = getenv(name);
     return e ? atoi(e) != 0 : dflt;
@@ -1232,14 +1078,13 @@ extern "C" int fed_logistic_glm_batched(
     if (K != 512 && K != 1024) return -4;
 
     // Variant.  v3 (glds tile-resident, 1x HBM traffic) is the default at
-    // K=1024: 0.89 ms vs v2's 1.035 / v1's 1.568 at 2e6x1024x16.  At K=512 the
-    // chunked v2 stays default: its 64-KB tiles already re-read through L2
+    // K=1024: 0.89 ms vs v2's 1.035 at 2e6x1024x16.  At K=512 the chunked
+    // v2 stays default: its 64-KB tiles already re-read through L2
     // (measured 0.567 ms ~= the 1x floor vs v3s 0.645 at 2e6x512 --
     // raw_r2/r2c12); FED_BATCHED_V3=1/0 forces either way.  The A/B
-    // baselines win over it: FED_BATCHED_LDS, then FED_BATCHED_V1.
-    enum { V_LDS, V_V1, V_V3, V_V2 } variant;
+    // baseline wins over it: FED_BATCHED_LDS.
+    enum { V_LDS, V_V3, V_V2 } variant;
     if (env_flag("FED_BATCHED_LDS", false)) variant = V_LDS;
-    else if (env_flag("FED_BATCHED_V1", false)) variant = V_V1;
     else if (env_flag("FED_BATCHED_V3", K == 1024)) variant = V_V3;
     else variant = V_V2;
 
@@ -1249,7 +1094,7 @@ extern "C" int fed_logistic_glm_batched(
     // phase B's re-read can hit L2 instead of HBM -- at the cost of half
     // the waves hiding phase A's stream latency.  v3/v3s and the LDS
     // variant hold one block per CU.
-    int cap = variant == V_V1 ? 304 : 512;
+    int cap = 512;
     if (const char* ge = getenv("FED_BATCHED_GRID")) {
         int v = atoi(ge);
         if (v >= 16 && v <= 768) cap = v;
@@ -1271,7 +1116,7 @@ extern "C" int fed_logistic_glm_batched(
     else if (variant == V_LDS)  // whole tile (~132 KB at K=1024), R^T | y, red
         lds_bytes = (BL_ROWS * (K + XPAD) + BCH * (BL_ROWS + RPAD) + 8) * 2 +
                     (BL_ROWS + 256) * 4 + 64;
-    else  // v1, v2: Theta, 2 chunk buffers, R^T | y, red
+    else  // v2: Theta, 2 chunk buffers, R^T | y, red
         lds_bytes = (BCH * (K + TPAD) + 2 * BL_ROWS * (BL_CHUNK + XPAD) +
                      BCH * (BL_ROWS + RPAD) + 8) * 2 +
                     (BL_ROWS + 256) * 4 + 64;
@@ -1288,15 +1133,17 @@ extern "C" int fed_logistic_glm_batched(
     } else if (variant == V_V2) {
         if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched_v2<1024>);
         else LAUNCH_BATCHED(k_logistic_glm_batched_v2<512>);
-    } else if (variant == V_LDS) {
+    } else {
         if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched_lds<1024>);
         else LAUNCH_BATCHED(k_logistic_glm_batched_lds<512>);
-    } else {
-        if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched<1024>);
-        else LAUNCH_BATCHED(k_logistic_glm_batched<512>);
     }
 #undef LAUNCH_BATCHED
     hipError_t kerr = hipGetLastError();
     if (kerr != hipSuccess) return (int)kerr;
-    return reduce_slab(workspace, grid, slab_cols, out, stream);
+
+    // slab -> out, zeroed first: the reduce kernel accumulates with atomics
+    // when it runs more than one chunk
+    hipError_t merr = hipMemsetAsync(out, 0, slab_cols * 8, stream);
+    if (merr != hipSuccess) return (int)merr;
+    return launch_colsum_reduce(workspace, grid, (int)slab_cols, out, stream);
 }
