@@ -59,8 +59,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .base import LogpGradModel
 from .fisher_vector import FisherVectorMixin
+from .shard import ShardGLMModel, _as_tensor
 
 __all__ = [
     "PoissonGLMModel",
@@ -112,17 +112,12 @@ def generate_gaussian_glm_dataset(
     return X, y, beta
 
 
-def _as_tensor(a) -> torch.Tensor:
-    return a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
-
-
-class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
-    """What the families share: the shard, zero-column padding to a kernel
-    size, the kernel/eager dispatch and the ``out=`` seam.  A family names
+class _GLMFamilyModel(FisherVectorMixin, ShardGLMModel):
+    """What the families share on top of the shard base: the offset, the
+    kernel/eager dispatch and the Fisher information.  A family names
     its ``_link`` and gives ``_terms`` (the eager per-row logp term and
     residual) and ``_logp_const``."""
 
-    param_names = ("beta",)
     _link: str = ""
 
     def __init__(
@@ -138,42 +133,21 @@ class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
     ) -> None:
         super().__init__(delay=delay)
         X, y = _as_tensor(X), _as_tensor(y)
-        if X.dim() != 2 or y.dim() != 1 or X.shape[0] != y.shape[0]:
-            raise ValueError("X must be [N,K] and y [N].")
-        if X.shape[1] < 1:
-            raise ValueError("X must have at least one column.")
+        self._check_shard(X, y)
         if offset is not None:
             offset = _as_tensor(offset)
             if offset.shape != y.shape:
                 raise ValueError("offset must be [N].")
-        if dtype is None:
-            dtype = X.dtype if X.is_floating_point() else torch.float64
-        if device is None:
-            device = X.device
+        device, dtype = self._placement(X, device, dtype)
         # y and offset: f32 (what the kernel reads) unless the shard is fp64
         self._acc_dtype = torch.float64 if dtype == torch.float64 else torch.float32
-        self._X = X.to(device=device, dtype=dtype).contiguous()
+        X = X.to(device=device, dtype=dtype)
         self._y = y.to(device=device, dtype=self._acc_dtype).contiguous()
         self._offset = (
             None if offset is None
             else offset.to(device=device, dtype=self._acc_dtype).contiguous()
         )
-        self._use_kernels = use_kernels
-        self._n, self._k = self._X.shape
-        self._k_pad = 0
-        if (use_kernels is None or use_kernels) and self._X.is_cuda:
-            from ..ops import glm_family_padded_k
-
-            # pad the feature dim to the next size the kernel is compiled
-            # for; zero columns change nothing: z is unaffected and their
-            # gradient is exactly 0.
-            k_eff = glm_family_padded_k(dtype, self._k)
-            if k_eff is not None and k_eff != self._k:
-                self._k_pad = k_eff - self._k
-                pad = torch.zeros(
-                    (self._n, self._k_pad), device=self._X.device, dtype=self._X.dtype
-                )
-                self._X = torch.cat([self._X, pad], dim=1).contiguous()
+        self._set_shard(X, use_kernels)
 
     # -- what a family provides -------------------------------------------
     def _terms(self, y: torch.Tensor, z: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -188,30 +162,8 @@ class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
     _sigma: float = 1.0
 
     # -- shared -------------------------------------------------------------
-    @property
-    def device(self):
-        return self._X.device
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._n)
-
-    @property
-    def n_features(self) -> int:
-        return int(self._k)
-
-    @property
-    def _k_eff(self) -> int:
-        """Feature dim as the kernel sees it (incl. zero padding)."""
-        return self._k + self._k_pad
-
-    @property
-    def fused_size(self) -> int:
-        """Layout of the fused fp64 output buffer: [logp, grad[K]]."""
-        return 1 + int(self._k)
-
     def _kernel_path(self) -> bool:
-        want = self._X.is_cuda if self._use_kernels is None else self._use_kernels
+        want = self._want_kernels()
         if want and self._use_kernels is None:
             from ..ops import glm_family_kernel_supports
 
@@ -243,28 +195,17 @@ class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
                 logp_const=self._logp_const,
             )
             if self._k_pad:
-                beta = torch.cat(
-                    [beta.to(torch.float32),
-                     torch.zeros(self._k_pad, dtype=torch.float32, device=beta.device)]
-                )
                 # ``out`` (if given) is sized [1 + k]; the kernel writes
                 # [1 + k_eff] -- evaluate into the kernel's own buffer and
                 # copy the un-padded slice over.
-                logp, grad = glm_family_logp_grad(self._X, self._y, beta, **kw)
-                grad = grad[: self._k]
-                if out is not None:
-                    out[0] = logp
-                    out[1:] = grad
-                    return out[0], [out[1:]]
+                logp, grad = glm_family_logp_grad(self._X, self._y, self._pad_rows(beta), **kw)
+                logp, grad = self._into_out(out, logp, grad[: self._k])
                 return logp, [grad]
             logp, grad = glm_family_logp_grad(self._X, self._y, beta, out=out, **kw)
             return logp, [grad]
         logp, grads = self._logp_grad_eager(beta)
-        if out is not None:
-            out[0] = logp
-            out[1:] = grads[0]
-            return out[0], [out[1:]]
-        return logp, grads
+        logp, grad = self._into_out(out, logp, grads[0])
+        return logp, [grad]
 
     def _logp_grad_eager(self, beta: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
         logp, G = self._logp_grad_batched_eager(beta.reshape(self._k, 1))
@@ -336,16 +277,12 @@ class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
         B = theta.shape[1]
         logp = torch.full((B,), self._logp_const, dtype=torch.float64, device=X.device)
         G = torch.zeros((self._k, B), dtype=torch.float64, device=X.device)
-        # large GPU shard in a narrow type: chunk the rows so the upcast of
-        # X stays O(chunk) instead of a second copy of a multi-GB shard
-        chunked = X.dtype != acc and X.is_cuda and self._n > 1 << 20
-        step = 1 << 21 if chunked else max(self._n, 1)
-        for s in range(0, self._n, step):
-            Xf = X[s : s + step].to(acc)
+        for rows in self._row_chunks(X.dtype != acc):
+            Xf = X[rows].to(acc)
             Z = Xf @ theta
             if self._offset is not None:
-                Z = Z + self._offset[s : s + step, None]
-            term, resid = self._terms(self._y[s : s + step, None], Z)
+                Z = Z + self._offset[rows, None]
+            term, resid = self._terms(self._y[rows, None], Z)
             logp += torch.sum(term, dim=0, dtype=torch.float64)
             G += (Xf.t() @ resid).to(torch.float64)
         return logp, G
@@ -377,10 +314,7 @@ class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
             kw = dict(link=self._link, offset=self._offset, sigma=self._sigma)
             beta = beta.to(device=self._X.device, dtype=torch.float32)
             if self._k_pad:
-                beta = torch.cat(
-                    [beta, torch.zeros(self._k_pad, dtype=torch.float32, device=beta.device)]
-                )
-                H = glm_family_fisher(self._X, beta, **kw)[: self._k, : self._k]
+                H = glm_family_fisher(self._X, self._pad_rows(beta), **kw)[: self._k, : self._k]
             elif out is not None and out.is_contiguous():
                 return glm_family_fisher(self._X, beta, out=out, **kw)
             else:
@@ -424,16 +358,12 @@ class _GLMFamilyModel(FisherVectorMixin, LogpGradModel):
         # short f32 chains on a GPU (one batched matmul per step, at most
         # 256 MB of chain results); fp64 data and the CPU's BLAS need none
         R = self._FISHER_CHAIN_ROWS if (X.is_cuda and acc != torch.float64) else 0
-        # chunked like _logp_grad_batched_eager: the upcast of X stays O(chunk)
-        chunked = X.dtype != acc and X.is_cuda and self._n > 1 << 20
-        step = 1 << 21 if chunked else max(self._n, 1)
-        if R:
-            step = min(step, R * max(1, (1 << 26) // (K * K)))
-        for s in range(0, self._n, step):
-            Xf = X[s : s + step].to(acc)
+        cap = R * max(1, (1 << 26) // (K * K)) if R else None
+        for rows in self._row_chunks(X.dtype != acc, cap):
+            Xf = X[rows].to(acc)
             z = Xf @ beta
             if self._offset is not None:
-                z = z + self._offset[s : s + step]
+                z = z + self._offset[rows]
             WX = self._weights(z)[:, None] * Xf
             full = (Xf.shape[0] // R) * R if R else 0
             if full:

@@ -31,8 +31,8 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .base import LogpGradModel
 from .fisher_vector import FisherVectorMixin
+from .shard import ShardGLMModel, _as_tensor
 
 __all__ = ["LogisticGLMModel", "generate_logistic_dataset"]
 
@@ -53,10 +53,9 @@ def generate_logistic_dataset(
     return X, y, beta
 
 
-class LogisticGLMModel(FisherVectorMixin, LogpGradModel):
+class LogisticGLMModel(FisherVectorMixin, ShardGLMModel):
     """Federated worker model: logistic regression on a private shard."""
 
-    param_names = ("beta",)
     # what FisherVectorMixin reads: the link of ops.glm_family_fisher_vector,
     # no offset, no noise scale
     _link = "logistic"
@@ -74,51 +73,21 @@ class LogisticGLMModel(FisherVectorMixin, LogpGradModel):
         delay: Optional[float] = None,
     ) -> None:
         super().__init__(delay=delay)
-        X = torch.as_tensor(np.asarray(X)) if not isinstance(X, torch.Tensor) else X
-        y = torch.as_tensor(np.asarray(y)) if not isinstance(y, torch.Tensor) else y
-        if dtype is None:
-            dtype = X.dtype if X.is_floating_point() else torch.float64
-        if device is None:
-            device = X.device
-        self._X = X.to(device=device, dtype=dtype).contiguous()
+        X, y = _as_tensor(X), _as_tensor(y)
+        device, dtype = self._placement(X, device, dtype)
+        X = X.to(device=device, dtype=dtype)
         self._y = y.to(device=device, dtype=dtype).contiguous()
-        self._use_kernels = use_kernels
-        if self._X.dim() != 2 or self._y.dim() != 1 or self._X.shape[0] != self._y.shape[0]:
-            raise ValueError("X must be [N,K] and y [N].")
-        self._n, self._k = self._X.shape
-        self._k_pad = 0
-        if (use_kernels is None or use_kernels) and self._X.is_cuda:
-            # pad the feature dim to the fused kernel's lane-slice granule
-            # (512 bf16 / 256 f32 per wave64 pass); zero columns change
-            # nothing: z is unaffected and their gradient is exactly 0.
-            granule = 512 if dtype == torch.bfloat16 else 256
-            rem = self._k % granule
-            if rem:
-                self._k_pad = granule - rem
-                pad = torch.zeros(
-                    (self._n, self._k_pad), device=self._X.device, dtype=self._X.dtype
-                )
-                self._X = torch.cat([self._X, pad], dim=1).contiguous()
+        self._check_shard(X, self._y, min_columns=0)
+        self._set_shard(X, use_kernels)
 
-    @property
-    def device(self):
-        return self._X.device
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._n)
-
-    @property
-    def n_features(self) -> int:
-        return int(self._k)
-
-    @property
-    def _k_eff(self) -> int:
-        """Feature dim as the kernel sees it (incl. zero padding)."""
-        return self._k + self._k_pad
+    def _padded_k(self) -> int:
+        # the fused kernel's lane-slice granule: 512 bf16 / 256 f32 per
+        # wave64 pass
+        granule = 512 if self._X.dtype == torch.bfloat16 else 256
+        return -(-self._k // granule) * granule
 
     def _kernel_path(self) -> bool:
-        want = self._X.is_cuda if self._use_kernels is None else self._use_kernels
+        want = self._want_kernels()
         if want and self._use_kernels is None:
             from ..ops import logistic_kernel_supports
 
@@ -134,11 +103,6 @@ class LogisticGLMModel(FisherVectorMixin, LogpGradModel):
                 return False
         return want
 
-    @property
-    def fused_size(self) -> int:
-        """Layout of the fused fp64 output buffer: [logp, grad[K]]."""
-        return 1 + int(self._k)
-
     # -- Fisher-vector product (FisherVectorMixin) ----------------------------
     @property
     def _acc_dtype(self) -> torch.dtype:
@@ -151,8 +115,7 @@ class LogisticGLMModel(FisherVectorMixin, LogpGradModel):
     def _fvp_kernel_path(self) -> bool:
         """No warning: a shape without a kernel (a padded K of 1536) is
         eager here as it is for ``logp_grad``, which says so."""
-        want = self._X.is_cuda if self._use_kernels is None else self._use_kernels
-        if not want:
+        if not self._want_kernels():
             return False
         from ..ops import glm_family_kernel_supports
 
@@ -168,28 +131,17 @@ class LogisticGLMModel(FisherVectorMixin, LogpGradModel):
             from ..ops import logistic_glm_logp_grad
 
             if self._k_pad:
-                beta = torch.cat(
-                    [beta.to(torch.float32),
-                     torch.zeros(self._k_pad, dtype=torch.float32, device=beta.device)]
-                )
                 # ``out`` (if given) is sized [1 + k]; the kernel writes
                 # [1 + k_eff] -- evaluate into the kernel's own buffer and
                 # copy the un-padded slice over.
-                logp, grad = logistic_glm_logp_grad(self._X, self._y, beta)
-                grad = grad[: self._k]
-                if out is not None:
-                    out[0] = logp
-                    out[1:] = grad
-                    return out[0], [out[1:]]
+                logp, grad = logistic_glm_logp_grad(self._X, self._y, self._pad_rows(beta))
+                logp, grad = self._into_out(out, logp, grad[: self._k])
                 return logp, [grad]
             logp, grad = logistic_glm_logp_grad(self._X, self._y, beta, out=out)
             return logp, [grad]
         logp, grads = self._logp_grad_eager(beta)
-        if out is not None:
-            out[0] = logp
-            out[1:] = grads[0]
-            return out[0], [out[1:]]
-        return logp, grads
+        logp, grad = self._into_out(out, logp, grads[0])
+        return logp, [grad]
 
     def logp_grad_batched(self, theta) -> Tuple[torch.Tensor, torch.Tensor]:
         """Evaluate 16 chains at once: theta[K,16] -> (logp[16], G[K,16]).
@@ -209,53 +161,34 @@ class LogisticGLMModel(FisherVectorMixin, LogpGradModel):
             from ..ops import logistic_glm_logp_grad_batched
 
             if self._k_pad:
-                theta = torch.cat(
-                    [theta.to(torch.float32),
-                     torch.zeros(self._k_pad, theta.shape[1], dtype=torch.float32,
-                                 device=theta.device)]
-                )
+                theta = self._pad_rows(theta)
             logp, G = logistic_glm_logp_grad_batched(self._X, self._y, theta)
             return logp, (G[: self._k] if self._k_pad else G)
         return self._logp_grad_batched_eager(theta)
 
     def _logp_grad_batched_eager(self, theta: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
         X, y = self._X[:, : self._k], self._y
-        acc_dtype = torch.float64 if X.dtype == torch.float64 else torch.float32
+        acc_dtype = self._acc_dtype
         theta = theta.to(device=X.device, dtype=acc_dtype)
-        if X.dtype == torch.bfloat16 and X.is_cuda and X.shape[0] > 1 << 20:
-            # large GPU shard: chunk the rows so the f32 upcast of X stays
-            # O(chunk) instead of materializing a full second copy of a
-            # multi-GB shard per call (this is the fallback path for K or B
-            # outside the MFMA kernel's coverage)
-            B = theta.shape[1]
-            logp = torch.zeros(B, dtype=torch.float64, device=X.device)
-            G = torch.zeros((self._k, B), dtype=torch.float64, device=X.device)
-            yf_all = y
-            step = 1 << 21
-            for s in range(0, X.shape[0], step):
-                Xf = X[s : s + step].to(acc_dtype)
-                yf = yf_all[s : s + step].to(acc_dtype)
-                Z = Xf @ theta
-                logp += torch.sum(
-                    yf[:, None] * Z - torch.nn.functional.softplus(Z),
-                    dim=0, dtype=torch.float64,
-                )
-                R = yf[:, None] - torch.sigmoid(Z)
-                G += (Xf.t() @ R).to(torch.float64)
-            return logp, G
-        Xf = X.to(acc_dtype)
-        yf = y.to(acc_dtype)
-        Z = Xf @ theta
-        logp = torch.sum(
-            yf[:, None] * Z - torch.nn.functional.softplus(Z), dim=0, dtype=torch.float64
-        )
-        R = yf[:, None] - torch.sigmoid(Z)
-        G = (Xf.t() @ R).to(torch.float64)
+        B = theta.shape[1]
+        logp = torch.zeros(B, dtype=torch.float64, device=X.device)
+        G = torch.zeros((self._k, B), dtype=torch.float64, device=X.device)
+        # this is the fallback path for K or B outside the MFMA kernel's
+        # coverage; only a bf16 shard counts as narrow here
+        for rows in self._row_chunks(X.dtype == torch.bfloat16):
+            Xf = X[rows].to(acc_dtype)
+            yf = y[rows].to(acc_dtype)
+            Z = Xf @ theta
+            logp += torch.sum(
+                yf[:, None] * Z - torch.nn.functional.softplus(Z), dim=0, dtype=torch.float64
+            )
+            R = yf[:, None] - torch.sigmoid(Z)
+            G += (Xf.t() @ R).to(torch.float64)
         return logp, G
 
     def _logp_grad_eager(self, beta: torch.Tensor) -> Tuple[torch.Tensor, List[torch.Tensor]]:
         X, y = self._X[:, : self._k], self._y
-        acc_dtype = torch.float64 if X.dtype == torch.float64 else torch.float32
+        acc_dtype = self._acc_dtype
         beta = beta.to(device=X.device, dtype=acc_dtype)
         Xf = X.to(acc_dtype)
         yf = y.to(acc_dtype)

@@ -34,8 +34,7 @@ from typing import List, Optional, Tuple
 import numpy as np
 import torch
 
-from .base import LogpGradModel
-from .glm import _as_tensor
+from .shard import ShardGLMModel, _as_tensor
 
 __all__ = ["SoftmaxGLMModel", "generate_softmax_dataset"]
 
@@ -66,12 +65,10 @@ def generate_softmax_dataset(
     return X, y, beta
 
 
-class SoftmaxGLMModel(LogpGradModel):
+class SoftmaxGLMModel(ShardGLMModel):
     """Federated worker model: multinomial logistic regression on a private
     shard of categorical responses (full parameterisation, see the module
     docstring for identifiability)."""
-
-    param_names = ("beta",)
 
     def __init__(
         self,
@@ -98,10 +95,7 @@ class SoftmaxGLMModel(LogpGradModel):
         """
         super().__init__(delay=delay)
         X, y = _as_tensor(X), _as_tensor(y)
-        if X.dim() != 2 or y.dim() != 1 or X.shape[0] != y.shape[0]:
-            raise ValueError("X must be [N,K] and y [N].")
-        if X.shape[1] < 1:
-            raise ValueError("X must have at least one column.")
+        self._check_shard(X, y)
         y64 = y.detach().to(device="cpu", dtype=torch.float64)
         if y64.numel():
             if not bool(torch.all(torch.isfinite(y64))) or bool(
@@ -121,53 +115,19 @@ class SoftmaxGLMModel(LogpGradModel):
             raise ValueError(
                 f"softmax y must be below n_classes={n_classes}, got {int(y64.max())}."
             )
-        if dtype is None:
-            dtype = X.dtype if X.is_floating_point() else torch.float64
-        if device is None:
-            device = X.device
+        device, dtype = self._placement(X, device, dtype)
         self._acc_dtype = torch.float64 if dtype == torch.float64 else torch.float32
-        self._X = X.to(device=device, dtype=dtype).contiguous()
+        X = X.to(device=device, dtype=dtype)
         self._labels = y64.to(device=device, dtype=torch.int64).contiguous()
         # what the kernel reads: labels as f32 (exact far beyond 16 classes)
         self._y = self._labels.to(torch.float32).contiguous()
         self._c = n_classes
-        self._use_kernels = use_kernels
-        self._n, self._k = self._X.shape
-        self._k_pad = 0
-        if (use_kernels is None or use_kernels) and self._X.is_cuda:
-            from ..ops import glm_family_padded_k
-
-            # zero columns change nothing: Z is unaffected and their
-            # gradient rows are exactly 0
-            k_eff = glm_family_padded_k(dtype, self._k)
-            if k_eff is not None and k_eff != self._k:
-                self._k_pad = k_eff - self._k
-                pad = torch.zeros(
-                    (self._n, self._k_pad), device=self._X.device, dtype=self._X.dtype
-                )
-                self._X = torch.cat([self._X, pad], dim=1).contiguous()
+        self._set_shard(X, use_kernels)
 
     # -- shape --------------------------------------------------------------
     @property
-    def device(self):
-        return self._X.device
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._n)
-
-    @property
-    def n_features(self) -> int:
-        return int(self._k)
-
-    @property
     def n_classes(self) -> int:
         return int(self._c)
-
-    @property
-    def _k_eff(self) -> int:
-        """Feature dim as the kernel sees it (incl. zero padding)."""
-        return self._k + self._k_pad
 
     @property
     def fused_size(self) -> int:
@@ -186,8 +146,7 @@ class SoftmaxGLMModel(LogpGradModel):
     def _kernel_path(self) -> bool:
         """bf16 shard on a ROCm device, padded K <= 1024 and C <= 16; K = 2048
         and C > 16 warn, f32 / f64 shards take eager silently."""
-        want = self._X.is_cuda if self._use_kernels is None else self._use_kernels
-        if not want or self._X.dtype != torch.bfloat16:
+        if not self._want_kernels() or self._X.dtype != torch.bfloat16:
             return False
         from ..ops import GLM_SOFTMAX_MAX_CLASSES, glm_family_batched_supports
 
@@ -227,9 +186,8 @@ class SoftmaxGLMModel(LogpGradModel):
         logp, G = self._eval(beta.reshape(self._k, self._c, 1))
         logp, G = logp[0], G[:, :, 0]
         if out is not None:
-            out[0] = logp
-            out[1:] = G.reshape(-1)
-            return out[0], [out[1:].view(self._k, self._c)]
+            logp, flat = self._into_out(out, logp, G.reshape(-1))
+            G = flat.view(self._k, self._c)
         return logp, [G]
 
     # -- several chains -----------------------------------------------------
@@ -297,16 +255,11 @@ class SoftmaxGLMModel(LogpGradModel):
         th = theta.to(device=X.device, dtype=acc).permute(0, 2, 1).reshape(K, B * C)
         logp = torch.zeros(B, dtype=torch.float64, device=X.device)
         G = torch.zeros((K, B * C), dtype=torch.float64, device=X.device)
-        # large GPU shard in a narrow type: chunk the rows so the upcast of
-        # X stays O(chunk) instead of a second copy of a multi-GB shard
-        chunked = X.dtype != acc and X.is_cuda and self._n > 1 << 20
-        step = 1 << 21 if chunked else max(self._n, 1)
-        if X.is_cuda:
-            # the [rows, B, C] temporaries: at most 2^27 elements each
-            step = min(step, max(1 << 10, (1 << 27) // (B * C)))
-        for s in range(0, self._n, step):
-            Xf = X[s : s + step].to(acc)
-            labels = self._labels[s : s + step]
+        # on a GPU the [rows, B, C] temporaries: at most 2^27 elements each
+        cap = max(1 << 10, (1 << 27) // (B * C)) if X.is_cuda else None
+        for chunk in self._row_chunks(X.dtype != acc, cap):
+            Xf = X[chunk].to(acc)
+            labels = self._labels[chunk]
             rows = Xf.shape[0]
             logsm = torch.log_softmax((Xf @ th).reshape(rows, B, C), dim=2)
             picked = logsm.gather(2, labels[:, None, None].expand(rows, B, 1))[:, :, 0]

@@ -48,6 +48,7 @@
 
 #include "fed_common.hpp"
 #include "glm_links.hpp"
+#include "row_group.hpp"
 
 // sum over the G lanes of a group; every lane of the group gets the total
 template <int G>
@@ -178,6 +179,14 @@ __global__ __launch_bounds__(256) void k_glm_family(
             for (int j = 0; j < VEC; ++j) gacc[c][j] += resid * xa[c][j];
     }
 
+    // The block epilogue below (fold, LDS sum, slab row) is written out in
+    // k_logistic_glm_reg (its G = 64 case) and k_glm_family_fvp as well.  A
+    // shared __forceinline__ helper was tried and withdrawn: the compiler
+    // simplifies a helper on its own before inlining it, and the ISA of all 54
+    // instantiations here moved (block order, the waves_per_block guard no
+    // longer shared with the logp loop, 2 SGPRs in two of them): see
+    // profiles/PROFILES.md "Row-group glue".
+
     // lanes with equal lane % G hold partials of the same columns
 #pragma unroll
     for (int c = 0; c < KITER; ++c)
@@ -219,41 +228,6 @@ __global__ __launch_bounds__(256) void k_glm_family(
     }
 }
 
-template <typename T, int G, int KITER, class Link>
-static void launch_glm_family(int grid, int block, int lds_bytes, hipStream_t stream,
-                              const void* X, const float* y, const float* offset,
-                              long long n_rows, const float* beta, LinkParams lp,
-                              double logp_const, double* out, float* workspace) {
-    hipLaunchKernelGGL((k_glm_family<T, G, KITER, Link>), dim3(grid), dim3(block), lds_bytes,
-                       stream, (const T*)X, y, offset, n_rows, beta, lp, logp_const, out,
-                       workspace);
-}
-
-// K -> (G, KITER) for one element type; false when K is not compiled
-template <typename T, class Link, typename... Args>
-static bool dispatch_glm_family_k(int K, Args... args) {
-    constexpr int VEC = VecTraits<T>::VEC;
-    switch (K / VEC) {  // the caller has checked K % VEC == 0
-        case 1:   launch_glm_family<T, 1, 1, Link>(args...); return true;
-        case 2:   launch_glm_family<T, 2, 1, Link>(args...); return true;
-        case 4:   launch_glm_family<T, 4, 1, Link>(args...); return true;
-        case 8:   launch_glm_family<T, 8, 1, Link>(args...); return true;
-        case 16:  launch_glm_family<T, 16, 1, Link>(args...); return true;
-        case 32:  launch_glm_family<T, 32, 1, Link>(args...); return true;
-        case 64:  launch_glm_family<T, 64, 1, Link>(args...); return true;
-        case 128: launch_glm_family<T, 64, 2, Link>(args...); return true;
-        case 256: launch_glm_family<T, 64, 4, Link>(args...); return true;
-        default:  return false;
-    }
-}
-
-template <class Link, typename... Args>
-static int dispatch_glm_family(int dtype, int K, Args... args) {
-    if (dtype == FED_BF16) return dispatch_glm_family_k<bf16_tag, Link>(K, args...) ? 0 : -4;
-    if (dtype == FED_F32) return dispatch_glm_family_k<float, Link>(K, args...) ? 0 : -4;
-    return -2;
-}
-
 extern "C" {
 
 // out = fp64[1+K] = {logp, grad...}; beta_f32 = fp32[K] device; y_f32 and
@@ -269,50 +243,22 @@ int fed_glm_family(
     int dtype, void* stream_v
 ) {
     hipStream_t stream = (hipStream_t)stream_v;
-    if (dtype != FED_BF16 && dtype != FED_F32) return -2;
-    if (link != FED_LINK_POISSON && link != FED_LINK_GAUSSIAN && link != FED_LINK_LOGISTIC)
-        return -5;
-    const int vec = dtype == FED_BF16 ? 8 : 4;
-    if (K < vec || K % vec != 0) return -4;
-    const int lanes = K / vec;  // G, or 64*KITER
-    if (lanes > 256 || (lanes & (lanes - 1)) != 0) return -4;
-    const int rows_per_step = lanes >= WAVE ? 1 : WAVE / lanes;
-
-    const int block = 256;
-    const int waves_per_block = block / WAVE;
-    const long long steps = (n_rows + rows_per_step - 1) / rows_per_step;
-    const long long pairs = (steps + 1) / 2;
-    int grid = pick_grid(pairs / waves_per_block + 1, 1);
-    if (grid > 1024) grid = 1024;
-    // FED_GLM_GRID caps the grid (tests reach a second grid-stride trip at
-    // small N with it); read per call
-    if (const char* ge = getenv("FED_GLM_GRID")) {
-        const int v = atoi(ge);
-        if (v >= 1 && v < grid) grid = v;
-    }
-    const long long need = (long long)grid * K * sizeof(float);
-    if (need > ws_bytes) grid = (int)(ws_bytes / ((long long)K * sizeof(float)));
-    if (grid < 1) return -3;
-    const int lds_bytes = ((K * 4 + 15) & ~15) + waves_per_block * 8;
+    RowGroupPlan plan;
+    if (const int bad = plan_row_group(dtype, link, K, n_rows, ws_bytes, plan)) return bad;
+    const int grid = plan.grid, block = plan.block;
+    const int lds_bytes = ((K * 4 + 15) & ~15) + block / WAVE * 8;
 
     hipError_t err = hipMemsetAsync(out, 0, (1 + K) * sizeof(double), stream);
     if (err != hipSuccess) return (int)err;
 
-    LinkParams lp;
-    lp.inv_s2 = (float)(1.0 / (sigma * sigma));
-    lp.half_inv_s2 = (float)(0.5 / (sigma * sigma));
-
-    int rc;
-#define DISPATCH_LINK(LINK)                                                              \
-    rc = dispatch_glm_family<LINK>(dtype, K, grid, block, lds_bytes, stream, X, y_f32,   \
-                                   offset_f32, n_rows, beta_f32, lp, logp_const, out,    \
-                                   workspace)
-    switch (link) {
-        case FED_LINK_POISSON:  DISPATCH_LINK(PoissonLink); break;
-        case FED_LINK_GAUSSIAN: DISPATCH_LINK(GaussianLink); break;
-        default:                DISPATCH_LINK(LogisticLink); break;
-    }
-#undef DISPATCH_LINK
+    const LinkParams lp = make_link_params(sigma);
+    const int rc = dispatch_row_group(dtype, link, K, [&](auto t, auto l, auto g, auto kiter) {
+        using T = typename decltype(t)::type;
+        using Link = typename decltype(l)::type;
+        hipLaunchKernelGGL((k_glm_family<T, decltype(g)::value, decltype(kiter)::value, Link>),
+                           dim3(grid), dim3(block), lds_bytes, stream, (const T*)X, y_f32,
+                           offset_f32, n_rows, beta_f32, lp, logp_const, out, workspace);
+    });
     if (rc != 0) return rc;
     hipError_t kerr = hipGetLastError();
     if (kerr != hipSuccess) return (int)kerr;

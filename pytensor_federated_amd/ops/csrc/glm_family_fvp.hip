@@ -49,6 +49,7 @@
 
 #include "fed_common.hpp"
 #include "glm_links.hpp"
+#include "row_group.hpp"
 
 // Sums over the G lanes of a group of several independent values at once;
 // every lane of the group gets the totals.  A plain xor butterfly moves every
@@ -239,6 +240,8 @@ __global__ __launch_bounds__(256) void k_glm_family_fvp(
         }
     }
 
+    // k_glm_family's block epilogue, kept as a copy: a shared helper changed
+    // the ISA (see the note there).
     // lanes with equal lane % G hold partials of the same columns
 #pragma unroll
     for (int c = 0; c < KITER; ++c)
@@ -270,40 +273,6 @@ __global__ __launch_bounds__(256) void k_glm_family_fvp(
     for (int col = threadIdx.x; col < K; col += blockDim.x) slab_row[col] = a_lds[col];
 }
 
-template <typename T, int G, int KITER, class Link>
-static void launch_glm_family_fvp(int grid, int block, int lds_bytes, hipStream_t stream,
-                                  const void* X, const float* offset, long long n_rows,
-                                  const float* beta, const float* v, LinkParams lp,
-                                  float* workspace) {
-    hipLaunchKernelGGL((k_glm_family_fvp<T, G, KITER, Link>), dim3(grid), dim3(block), lds_bytes,
-                       stream, (const T*)X, offset, n_rows, beta, v, lp, workspace);
-}
-
-// K -> (G, KITER) for one element type; false when K is not compiled
-template <typename T, class Link, typename... Args>
-static bool dispatch_glm_family_fvp_k(int K, Args... args) {
-    constexpr int VEC = VecTraits<T>::VEC;
-    switch (K / VEC) {  // the caller has checked K % VEC == 0
-        case 1:   launch_glm_family_fvp<T, 1, 1, Link>(args...); return true;
-        case 2:   launch_glm_family_fvp<T, 2, 1, Link>(args...); return true;
-        case 4:   launch_glm_family_fvp<T, 4, 1, Link>(args...); return true;
-        case 8:   launch_glm_family_fvp<T, 8, 1, Link>(args...); return true;
-        case 16:  launch_glm_family_fvp<T, 16, 1, Link>(args...); return true;
-        case 32:  launch_glm_family_fvp<T, 32, 1, Link>(args...); return true;
-        case 64:  launch_glm_family_fvp<T, 64, 1, Link>(args...); return true;
-        case 128: launch_glm_family_fvp<T, 64, 2, Link>(args...); return true;
-        case 256: launch_glm_family_fvp<T, 64, 4, Link>(args...); return true;
-        default:  return false;
-    }
-}
-
-template <class Link, typename... Args>
-static int dispatch_glm_family_fvp(int dtype, int K, Args... args) {
-    if (dtype == FED_BF16) return dispatch_glm_family_fvp_k<bf16_tag, Link>(K, args...) ? 0 : -4;
-    if (dtype == FED_F32) return dispatch_glm_family_fvp_k<float, Link>(K, args...) ? 0 : -4;
-    return -2;
-}
-
 extern "C" {
 
 // out = fp64[K] = X^T (w * (X v)), or the diagonal sum_r w_r x_rk^2 when
@@ -319,45 +288,23 @@ int fed_glm_family_fvp(
     int dtype, void* stream_v
 ) {
     hipStream_t stream = (hipStream_t)stream_v;
-    if (dtype != FED_BF16 && dtype != FED_F32) return -2;
-    if (link != FED_LINK_POISSON && link != FED_LINK_GAUSSIAN && link != FED_LINK_LOGISTIC)
-        return -5;
-    const int vec = dtype == FED_BF16 ? 8 : 4;
-    if (K < vec || K % vec != 0) return -4;
-    const int lanes = K / vec;  // G, or 64*KITER
-    if (lanes > 256 || (lanes & (lanes - 1)) != 0) return -4;
-    const int rows_per_step = lanes >= WAVE ? 1 : WAVE / lanes;
-
-    // the grid choice of fed_glm_family, FED_GLM_GRID included
-    const int block = 256;
-    const int waves_per_block = block / WAVE;
-    const long long steps = (n_rows + rows_per_step - 1) / rows_per_step;
-    const long long pairs = (steps + 1) / 2;
-    int grid = pick_grid(pairs / waves_per_block + 1, 1);
-    if (grid > 1024) grid = 1024;
-    if (const char* ge = getenv("FED_GLM_GRID")) {
-        const int g = atoi(ge);
-        if (g >= 1 && g < grid) grid = g;
-    }
-    const long long need = (long long)grid * K * sizeof(float);
-    if (need > ws_bytes) grid = (int)(ws_bytes / ((long long)K * sizeof(float)));
-    if (grid < 1) return -3;
+    // the launch plan of fed_glm_family, FED_GLM_GRID included
+    RowGroupPlan plan;
+    if (const int bad = plan_row_group(dtype, link, K, n_rows, ws_bytes, plan)) return bad;
+    const int grid = plan.grid, block = plan.block;
     const int lds_bytes = (K * 4 + 15) & ~15;
 
     hipError_t err = hipMemsetAsync(out, 0, K * sizeof(double), stream);
     if (err != hipSuccess) return (int)err;
 
     const LinkParams lp = make_link_params(sigma);
-    int rc;
-#define DISPATCH_LINK(LINK)                                                                  \
-    rc = dispatch_glm_family_fvp<LINK>(dtype, K, grid, block, lds_bytes, stream, X,          \
-                                       offset_f32, n_rows, beta_f32, v_f32, lp, workspace)
-    switch (link) {
-        case FED_LINK_POISSON:  DISPATCH_LINK(PoissonLink); break;
-        case FED_LINK_GAUSSIAN: DISPATCH_LINK(GaussianLink); break;
-        default:                DISPATCH_LINK(LogisticLink); break;
-    }
-#undef DISPATCH_LINK
+    const int rc = dispatch_row_group(dtype, link, K, [&](auto t, auto l, auto g, auto kiter) {
+        using T = typename decltype(t)::type;
+        using Link = typename decltype(l)::type;
+        hipLaunchKernelGGL((k_glm_family_fvp<T, decltype(g)::value, decltype(kiter)::value, Link>),
+                           dim3(grid), dim3(block), lds_bytes, stream, (const T*)X, offset_f32,
+                           n_rows, beta_f32, v_f32, lp, workspace);
+    });
     if (rc != 0) return rc;
     hipError_t kerr = hipGetLastError();
     if (kerr != hipSuccess) return (int)kerr;

@@ -119,6 +119,7 @@ __global__ __launch_bounds__(256) void k_logistic_glm_reg(
     }
 
     // cross-wave grad reduction in LDS (dynamic: K floats), then one slab row
+    // (the G = 64 case of k_glm_family's epilogue; why it is a copy: note there)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* g_lds = reinterpret_cast<float*>(smem);                  // [K]
     double* l_lds = reinterpret_cast<double*>(smem + ((K * 4 + 15) & ~15));  // [waves]

@@ -1,6 +1,6 @@
 // Batched (16-chain) logistic GLM on CDNA4 (gfx950) matrix cores: the MFMA
 // fragment-map probe, the kernels that ship (v3 at K=1024, v2 at K=512, v3s
-// as an opt-in), one A/B baseline (whole-tile LDS) and their dispatcher.
+// as an opt-in) and their dispatcher.
 // Every kernel here is covered by the exact-probe tests.  Shared pieces and
 // the overview of the GLM units are in fed_common.hpp.
 //
@@ -10,11 +10,12 @@
 // 2x-traffic floor; 0.567 at K=512, where it is the default); v3, a
 // tile-resident LDS-DMA pipeline that reads X once, 0.878 (~0.95 same-box
 // against its successor); v3 on the transpose-read image, 0.89, the K=1024
-// default.  The LDS-resident whole-tile variant lost its round-1 A/B to v1
-// (no figure recorded).  The scalar-gather image of v3, its instrumented
-// build and the two environment flags that selected them last exist at
-// commit 5e9376b.  v1 and the flag that selected it (FED_BATCHED_V1) last
-// exist at commit ebb4f6a.
+// default.  The scalar-gather image of v3, its instrumented build and the
+// two environment flags that selected them last exist at commit 5e9376b.
+// v1 and the flag that selected it (FED_BATCHED_V1) last exist at commit
+// ebb4f6a.  The LDS-resident whole-tile variant, which lost its round-1 A/B
+// to v1 (no figure recorded), and its flag (FED_BATCHED_LDS) last exist at
+// commit 84bf623.
 
 #include "fed_common.hpp"
 
@@ -89,8 +90,8 @@ extern "C" int fed_mfma_probe(const void* A, const void* B, void* D, void* strea
 // B[k=(l>>4)*8+j][j=l&15], D[col=l&15][row=(l>>4)*4+r].
 
 #define BCH 16           // chains per call
-#define BL_ROWS 64       // rows per block tile (v2, whole-tile LDS)
-#define BL_CHUNK 128     // K columns per chunk (v2, whole-tile LDS)
+#define BL_ROWS 64       // rows per block tile (v2)
+#define BL_CHUNK 128     // K columns per chunk (v2)
 #define XPAD 8           // X_lds row pad (elems): stride 272 B, b128-clean
 #define TPAD 8           // Theta row pad: stride 2064+16 B
 #define RPAD 8           // R_T row pad: stride 144 B
@@ -937,130 +938,8 @@ __global__ __launch_bounds__(256) void k_logistic_glm_batched_v3(
 }
 
 // ---------------------------------------------------------------------------
-// Batched logistic, LDS-resident-tile variant: phase B never re-reads HBM
+// Dispatcher
 // ---------------------------------------------------------------------------
-// The chunked variant's phase-B re-read misses L2 (2 blocks/CU x 32 CUs x
-// 128 KB tiles = 8 MB active per 4 MB XCD L2) -> ~2x HBM traffic.  Here ONE
-// block per CU holds its whole [64][K] tile in LDS (132 KB at K=1024),
-// stages it once with a deep load pipeline, and runs both MFMA phases out
-// of LDS.  Theta fragments read straight from L2 (32 KB, resident).
-
-template <int K>
-__global__ __launch_bounds__(256, 1) void k_logistic_glm_batched_lds(
-    const unsigned short* __restrict__ X,   // [N][K] bf16
-    const unsigned short* __restrict__ y,   // [N] bf16
-    long long n_rows,
-    const unsigned short* __restrict__ theta_t,  // [BCH][K] bf16
-    float* __restrict__ slab                     // [grid][BCH + K*BCH]
-) {
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    constexpr int n_chunks = K / BL_CHUNK;
-    constexpr int x_stride = K + XPAD;
-
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    unsigned short* x_lds = (unsigned short*)smem;              // [BL_ROWS][K+XPAD]
-    unsigned short* rt_lds = x_lds + BL_ROWS * x_stride;        // [BCH][BL_ROWS+RPAD]
-    const int rt_stride = BL_ROWS + RPAD;
-    float* y_lds = (float*)(rt_lds + BCH * rt_stride + 8);      // [BL_ROWS]
-    float* red_lds = y_lds + BL_ROWS;                           // [256]
-
-    f32x4_t g_acc[n_chunks * 2];
-#pragma unroll
-    for (int t = 0; t < n_chunks * 2; ++t) g_acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-    float logp_acc = 0.f;
-
-    const long long n_tiles = (n_rows + BL_ROWS - 1) / BL_ROWS;
-    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const long long row0 = tile * BL_ROWS;
-        if (threadIdx.x < BL_ROWS) {
-            const long long r = row0 + threadIdx.x;
-            y_lds[threadIdx.x] = r < n_rows ? bf16_bits_to_f32(y[r]) : 0.f;
-        }
-        // ---- stage the WHOLE tile: 512 B per thread, 32 deep loads ----
-        {
-            const int r = threadIdx.x / 16;          // owns rows r, r+16, ...
-            const int k0 = (threadIdx.x % 16) * 8;   // k column start
-#pragma unroll
-            for (int rr = 0; rr < 4; ++rr) {
-                const long long row = row0 + r + rr * 16;
-#pragma unroll
-                for (int kk = 0; kk < K / 128; ++kk) {
-                    U4 val = {0, 0, 0, 0};
-                    if (row < n_rows)
-                        val = *(const U4*)&X[row * (long long)K + kk * 128 + k0];
-                    *(U4*)&x_lds[(r + rr * 16) * x_stride + kk * 128 + k0] = val;
-                }
-            }
-        }
-        __syncthreads();
-
-        // ---- phase A: Z (LDS x, L2 theta) ----
-        f32x4_t z_acc = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int ks = 0; ks < K / 32; ++ks) {
-            frag_u a, b;
-            const int arow = wid * 16 + (lane & 15);
-            const int ak = ks * 32 + (lane >> 4) * 8;
-            a.q = *(U4*)&x_lds[arow * x_stride + ak];
-            b.q = *(const U4*)&theta_t[(lane & 15) * K + ak];
-            z_acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, z_acc, 0, 0, 0);
-        }
-
-        // ---- logp + R ----
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row_in_wave = (lane >> 4) * 4 + r;
-            const int row_in_tile = wid * 16 + row_in_wave;
-            const long long row = row0 + row_in_tile;
-            const int chain = lane & 15;
-            float z = z_acc[r];
-            float yv = y_lds[row_in_tile];
-            float resid = 0.f;
-            if (row < n_rows) resid = logistic_term_resid(z, yv, logp_acc);
-            rt_lds[chain * rt_stride + row_in_tile] = f32_to_bf16_rne_bits(resid);
-        }
-        __syncthreads();  // R complete
-
-        // ---- phase B: G += X^T R (all LDS) ----
-#pragma unroll
-        for (int c = 0; c < n_chunks; ++c) {
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) {
-                const int kcol0 = c * BL_CHUNK + wid * 32 + t2 * 16;
-                f32x4_t acc = g_acc[c * 2 + t2];
-#pragma unroll
-                for (int rs = 0; rs < 2; ++rs) {
-                    frag_u a, b;
-                    const int kcol = kcol0 + (lane & 15);
-                    const int arow0 = rs * 32 + (lane >> 4) * 8;
-#pragma unroll
-                    for (int j = 0; j < 8; ++j)
-                        a.u[j] = x_lds[(arow0 + j) * x_stride + kcol];
-                    b.q = *(U4*)&rt_lds[(lane & 15) * rt_stride + rs * 32 + (lane >> 4) * 8];
-                    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a.v, b.v, acc, 0, 0, 0);
-                }
-                g_acc[c * 2 + t2] = acc;
-            }
-        }
-        __syncthreads();  // x_lds/rt_lds reuse next tile
-    }
-
-    // ---- epilogue (same slab layout as the chunked variant) ----
-    float* g_slab = epilogue_logp<K>(slab, red_lds, logp_acc);
-#pragma unroll
-    for (int c = 0; c < n_chunks; ++c) {
-#pragma unroll
-        for (int t2 = 0; t2 < 2; ++t2) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int kcol = c * BL_CHUNK + wid * 32 + t2 * 16 + (lane >> 4) * 4 + r;
-                const int chain = lane & 15;
-                g_slab[(long long)kcol * BCH + chain] = g_acc[c * 2 + t2][r];
-            }
-        }
-    }
-}
 
 static bool env_flag(const char* name, bool dflt) {
     const char* e = getenv(name);
@@ -1081,19 +960,15 @@ extern "C" int fed_logistic_glm_batched(
     // K=1024: 0.89 ms vs v2's 1.035 at 2e6x1024x16.  At K=512 the chunked
     // v2 stays default: its 64-KB tiles already re-read through L2
     // (measured 0.567 ms ~= the 1x floor vs v3s 0.645 at 2e6x512 --
-    // raw_r2/r2c12); FED_BATCHED_V3=1/0 forces either way.  The A/B
-    // baseline wins over it: FED_BATCHED_LDS.
-    enum { V_LDS, V_V3, V_V2 } variant;
-    if (env_flag("FED_BATCHED_LDS", false)) variant = V_LDS;
-    else if (env_flag("FED_BATCHED_V3", K == 1024)) variant = V_V3;
-    else variant = V_V2;
+    // raw_r2/r2c12); FED_BATCHED_V3=1/0 forces either way.
+    const bool v3 = env_flag("FED_BATCHED_V3", K == 1024);
 
     // Grid.  v2 runs 2 blocks/CU (71 KB LDS); 512 blocks covers every CU
     // twice.  FED_BATCHED_GRID overrides for the L2-residency A/B: at 256
     // (1 block/CU) a block's whole 128 KB tile fits its XCD L2 share, so
     // phase B's re-read can hit L2 instead of HBM -- at the cost of half
-    // the waves hiding phase A's stream latency.  v3/v3s and the LDS
-    // variant hold one block per CU.
+    // the waves hiding phase A's stream latency.  v3/v3s hold one block
+    // per CU.
     int cap = 512;
     if (const char* ge = getenv("FED_BATCHED_GRID")) {
         int v = atoi(ge);
@@ -1105,17 +980,13 @@ extern "C" int fed_logistic_glm_batched(
     if ((long long)grid * slab_cols * 4 > ws_bytes)
         grid = (int)(ws_bytes / (slab_cols * 4));
     if (grid < 1) return -3;
-    if (variant == V_V3 && grid > 256) grid = 256;
-    if (variant == V_LDS && grid > 304) grid = 304;
+    if (v3 && grid > 256) grid = 256;
 
     // Dynamic LDS: u16 elements, then fp32 words, then alignment slack.
     int lds_bytes;
-    if (variant == V_V3)  // Theta, 3 half/tile buffers, R^T | zc, red
+    if (v3)  // Theta, 3 half/tile buffers, R^T | zc, red
         lds_bytes = (BCH * (K + TPAD) + 3 * V3_ROWS * V3_HALF + BCH * (V3_ROWS + RPAD)) * 2 +
                     (4 * V3_ROWS * BCH + 256) * 4 + 64;
-    else if (variant == V_LDS)  // whole tile (~132 KB at K=1024), R^T | y, red
-        lds_bytes = (BL_ROWS * (K + XPAD) + BCH * (BL_ROWS + RPAD) + 8) * 2 +
-                    (BL_ROWS + 256) * 4 + 64;
     else  // v2: Theta, 2 chunk buffers, R^T | y, red
         lds_bytes = (BCH * (K + TPAD) + 2 * BL_ROWS * (BL_CHUNK + XPAD) +
                      BCH * (BL_ROWS + RPAD) + 8) * 2 +
@@ -1126,16 +997,13 @@ extern "C" int fed_logistic_glm_batched(
                        (const unsigned short*)X, (const unsigned short*)y, n_rows,    \
                        (const unsigned short*)theta_t_bf16, workspace, ##__VA_ARGS__)
 
-    if (variant == V_V3) {
+    if (v3) {
         const int nt_on = env_flag("FED_V3_NT", true);  // stream-once data: nt default
         if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched_v3, nt_on);
         else LAUNCH_BATCHED(k_logistic_glm_batched_v3s<512>, nt_on);
-    } else if (variant == V_V2) {
+    } else {
         if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched_v2<1024>);
         else LAUNCH_BATCHED(k_logistic_glm_batched_v2<512>);
-    } else {
-        if (K == 1024) LAUNCH_BATCHED(k_logistic_glm_batched_lds<1024>);
-        else LAUNCH_BATCHED(k_logistic_glm_batched_lds<512>);
     }
 #undef LAUNCH_BATCHED
     hipError_t kerr = hipGetLastError();

@@ -18,7 +18,7 @@ pytestmark = pytest.mark.gpu
 from pytensor_federated_amd.models import GaussianLinearModel, LogisticGLMModel
 
 BATCHED_ENV = (
-    "FED_BATCHED_V3", "FED_BATCHED_LDS",
+    "FED_BATCHED_V3",
     "FED_BATCHED_GRID", "FED_V3_NT",
 )
 
@@ -28,8 +28,6 @@ BATCHED_VARIANTS = {
     "v2_k1024": (1024, {"FED_BATCHED_V3": "0"}),
     "v2_k512": (512, {}),                             # default at K=512
     "v3s_k512": (512, {"FED_BATCHED_V3": "1"}),
-    "lds_k1024": (1024, {"FED_BATCHED_LDS": "1"}),
-    "lds_k512": (512, {"FED_BATCHED_LDS": "1"}),
 }
 
 
